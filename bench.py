@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
-"""bench.py - EM slices/sec (1024^2, Hiera-L) on N MI355X, plus the roofline of the dominant kernel and a
-CPU baseline timed beside it.
+"""bench.py - EM slices/sec (1024^2, Hiera-L) on N MI355X; with --full also the roofline of the dominant kernel, the other
+precisions and configurations, and a CPU baseline timed beside it.
+
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the result line;
+`--dump-outputs DIR` writes what the last timed step computed (label plane, mask count, encoder features) as .npy files.  Everything else the line
+used to carry (stitch, hipGraph A/B, IoU pruning, per-class profile and roofline, encoder-only, tail, video, precision, volume512,
+alt_dtypes, fitted_decoder, cpu_baseline) runs only under `--full`, where the --no-* options select among them.
 
 A "step" is one pass of the hot path over one synthetic 1024x1024 uint16 EM slice already resident in HBM:
 K0 prepare (prep.prepare) -> automatic mask generation with SABER's cfgAMG defaults (crop_n_layers=2: 21 crops,
@@ -64,6 +69,13 @@ def parse():
     ap.add_argument("--no-encoder-only", action="store_true", help="skip the extra encoder-only timing (profiling runs: keeps the kernel population of the trace = whole slices)")
     ap.add_argument("--no-video", action="store_true", help="skip the extra measurement of the SAM2 video (memory) path, SURVEY.md 8f-1")
     ap.add_argument("--no-tail", action="store_true", help="skip the extra measurement of the post-filter tail on a slice with a few hundred masks")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the stitch and, at N = 1, hipGraph A/B, IoU pruning, "
+                    "per-class profile and roofline, encoder-only, tail, video, precision, volume512, alt_dtypes, fitted_decoder, cpu_baseline (the --no-* "
+                    "options above select among them).  Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (rank 0): "
+                    "DIR/label_plane.npy (the 1024x1024 label plane, float32), DIR/n_masks.npy (masks painted, float64), the encoder features of its "
+                    "whole-slice crop (DIR/image_embed.npy, feat_s1.npy, feat_s0.npy) and a seeded sample of every crop's image embedding "
+                    "(DIR/crops_image_embed_sample.npy); about 22 MB")
     return ap.parse_args()
 
 
@@ -228,7 +240,7 @@ def precision_check(weights, img, operands="bf16"):
 
 
 def full_size_keys(a, engines, pool, make_amg_params, Z=512, window=24):
-    """BASELINE configs[3] at FULL size on this one GPU, inside the default line: a 1024 x 1024 x Z tomogram resident in HBM
+    """BASELINE configs[3] at FULL size on this one GPU, inside the --full line: a 1024 x 1024 x Z tomogram resident in HBM
     -> the z-loop on the headline's engine handles -> label planes -> 3-D connected components on the device -> uint32 labels on the host, with the
     size-independent checks of tests/test_gpu_config34_volume.py::test_config3_512_slices_full_size asserted on the result.  The score thresholds
     are that test's (pred_iou 0.5, stability 0.8: the seeded, untrained decoder leaves nothing at cfgAMG's own), so paint / dedup / stitch run on
@@ -284,7 +296,7 @@ def full_size_keys(a, engines, pool, make_amg_params, Z=512, window=24):
     pairs = np.unique(np.stack([host[sel].astype(np.int64), lw[sel].astype(np.int64)], 1), axis=0)
     assert len(np.unique(pairs[:, 0])) == len(pairs)
     checks["asserted"] = "ids contiguous per plane; 8 slices at the 8-rank chunk bounds recomputed standalone bit-equal; every label >= 1000 voxels and inside the painted voxels; device stitch == scipy on a 24-plane window; window components map to ONE global label each"
-    return {"what": f"BASELINE configs[3] at full size on ONE GPU inside the default line: 1024x1024x{Z} uint16 tomogram (the synthetic slices cycled along z) -> z-loop on the headline's "
+    return {"what": f"BASELINE configs[3] at full size on ONE GPU inside the --full line: 1024x1024x{Z} uint16 tomogram (the synthetic slices cycled along z) -> z-loop on the headline's "
                     f"{len(engines)} engine handles -> label planes -> 3-D connected components on the device -> uint32 labels on the host; AMG score thresholds of "
                     f"tests/test_gpu_config34_volume.py (pred_iou 0.5, stability 0.8) so that the planes carry labels",
             "slices": Z, "slices_per_s": Z / dt, "seconds": dt, "labels": K,
@@ -537,10 +549,13 @@ def main():
     pool = [torch.from_numpy(saber_ref.synthetic_slice(seed=1000 * rank + i)).cuda() for i in range(2)]
     torch.cuda.synchronize()
 
+    masks_of_step = {}
+
     def step(i, planes=None, engine=None):
         plane, n_masks = segment_slice_to_plane(engine or eng, pool[i % len(pool)], params, min_mask_area=50)
         if planes is not None:
             planes[i] = plane
+            masks_of_step[i] = n_masks
         return n_masks
 
     engines = [eng] + [mk_engine(a.dtype) for _ in range(a.workers - 1)]
@@ -584,7 +599,7 @@ def main():
             t.join()
         return sum(totals)
 
-    img01_cpu = eng.prepare(pool[0]).cpu().numpy() if (rank == 0 and world == 1 and not a.no_cpu_baseline) else None      # (input of the CPU baseline leg)
+    img01_cpu = eng.prepare(pool[0]).cpu().numpy() if (rank == 0 and world == 1 and a.full and not a.no_cpu_baseline) else None      # (input of the CPU baseline leg)
     # N > 1 without an explicit workload: the north star's 512-slice strong-scaling tomogram is the line's `value`; the weak-scaling K steps of
     # rounds 1-4 run first (they also warm every handle) and ride along as the extra key `weak_scaling`.
     north_star = world > 1 and not a.weak and a.volume == 0 and a.tomograms == 0
@@ -629,6 +644,21 @@ def main():
         t = torch.tensor([dt], device=dev_, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and a.dump_outputs:
+        # what the last timed step computed: the slice's uint16 label plane and the number of masks painted into it (what its caller
+        # receives; with the seeded weights cfgAMG's thresholds leave 0-1 masks, so the plane is often empty), and the encoder features
+        # that step left in the engine handle that ran it - read out after the timed region, not recomputed: every tensor of crop 0
+        # (the whole slice) and a fixed, seeded sample of the image embedding of every crop
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        last = a.steps - 1
+        e_last = engines[last % len(engines)]
+        dump = {"label_plane": planes[last].cpu().numpy().astype(np.float32), "n_masks": np.array([masks_of_step[last]], dtype=np.float64)}
+        dump.update({k: v.cpu().numpy() for k, v in e_last.get_features(0).items()})
+        n_crops = min(a.max_images, 1 + sum((2 ** (l + 1)) ** 2 for l in range(a.crop_n_layers)))
+        idx = np.sort(np.random.default_rng(0).choice(256 * 64 * 64, 16384, replace=False))
+        dump["crops_image_embed_sample"] = np.stack([e_last.get_features(s)["image_embed"].flatten().cpu().numpy()[idx] for s in range(n_crops)])
+        for k, v in dump.items():
+            np.save(os.path.join(a.dump_outputs, f"{k}.npy"), v.astype(np.float32 if v.dtype != np.float64 else np.float64))
 
     out = None
     if rank == 0:
@@ -674,7 +704,7 @@ def main():
             e_.close()
         dist.destroy_process_group()
         return
-    if rank == 0:
+    if rank == 0 and a.full:
         # the stitch that follows the gather (utils.separate_masks, propagation.py:189) on the device; reported beside the metric, not in it
         vol = (gathered if world > 1 else planes).view(torch.int16)
         eng.separate_masks(vol, 100)
@@ -684,7 +714,7 @@ def main():
         torch.cuda.synchronize()
         out["stitch"] = {"what": "3-D connected components of the gathered label planes on rank 0's GPU (saber_separate_masks)",
                          "slices": int(vol.shape[0]), "ms": (time.perf_counter() - t0) * 1e3, "labels": n_lab}
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_tail:
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_tail:
         # hipGraph replay A/B on the same handle (the headline above runs with replay on unless SABER_AMD_GRAPHS=0)
         ab = {}
         for name, on in (("eager", False), ("graphs", True)):
@@ -701,7 +731,7 @@ def main():
         cap, rep = eng.graph_stats()
         out["hipgraph"] = dict(ab, what=f"same step, 6 slices each over the {len(engines)} engine handle(s) of the headline, launch sequences issued eagerly vs replayed from hipGraphs (encoder pass + each decoder batch)",
                                sequences_captured=cap, replays_so_far=rep, headline_uses_graphs=os.environ.get("SABER_AMD_GRAPHS", "1") != "0")
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_tail:
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_tail:
         # the production default: IoU pruning of the m2m pass on (results identical, tests/test_gpu_graphs.py); NOT the headline, see above
         for e_ in engines:
             e_.set_iou_pruning(True)
@@ -718,7 +748,7 @@ def main():
                               "ms_per_slice": dtp * 1e3, "slices_per_s": 1.0 / dtp, "m2m_candidates": seen, "pruned": pruned, "pruned_fraction": (pruned / seen) if seen else None}
         for e_ in engines:
             e_.set_iou_pruning(False)
-    if rank == 0 and world == 1 and not a.no_profile:
+    if rank == 0 and world == 1 and a.full and not a.no_profile:
         eng.profile_begin()
         step(0)
         prof = eng.profile_end()
@@ -766,7 +796,7 @@ def main():
         mp = prof["mask_post"]
         if mp["ms"] > 0:
             out["mask_post_hbm"] = {"bound": "hbm", "achieved": mp["bytes"] / (mp["ms"] * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s"}
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_encoder_only:
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_encoder_only:
         # encoder-only figure (the north star's roofline target is defined on the Hiera-L encoder)
         img = eng.prepare(pool[0])
         reps, nb = 3, a.max_images
@@ -780,30 +810,30 @@ def main():
         te = (time.perf_counter() - t0) / (reps * nb)
         out["encoder_only"] = {"passes_per_s": 1.0 / te, "ms_per_pass": te * 1e3, "batch": nb, "algorithmic_tflops": eng.encoder_flops() / te / 1e12,
                                "frac_of_bf16_peak": eng.encoder_flops() / te / 2.5e15}
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_tail:
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_tail:
         try:
             out["tail"] = tail_mode(eng, pool, a, segment_slice_to_plane, make_amg_params)
         except Exception as ex:     # the extra key must never take the headline down with it
             out["tail"] = {"error": str(ex)[:300]}
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_video and a.dtype == "bf16":
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_video and a.dtype == "bf16":
         try:        # the next row of the scope table: frames per second of the memory path, beside the metric, never in it
             sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
             import video_bench
             out["propagation"] = video_bench.run("large", 32)
         except Exception as ex:
             out["propagation"] = {"error": str(ex)[:300]}
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_tail and a.dtype in ("bf16", "fp16"):
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_tail and a.dtype in ("bf16", "fp16"):
         try:        # what the 16-bit operands of the headline cost against the engine's exact (fp32) mode on this slice; never part of `value`
             out["precision"] = precision_check(weights, eng.prepare(pool[0]), a.dtype)
         except Exception as ex:
             out["precision"] = {"error": str(ex)[:300]}
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_tail and not a.no_volume512:
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_tail and not a.no_volume512:
         try:        # configs[3] at full size on the headline's handles (about 75 s); never part of `value`
             out["volume512"] = full_size_keys(a, engines, pool, make_amg_params)
         except Exception as ex:
             out["volume512"] = {"error": f"{type(ex).__name__}: {str(ex)[:300]}"}
-    if rank == 0 and world == 1 and not a.no_profile and not a.no_tail and not a.no_alt_dtypes and a.dtype == "bf16":
-        # The other arithmetic modes as extra keys of the default line, each on fresh handles after the headline's were closed
+    if rank == 0 and world == 1 and a.full and not a.no_profile and not a.no_tail and not a.no_alt_dtypes and a.dtype == "bf16":
+        # The other arithmetic modes as extra keys of the --full line, each on fresh handles after the headline's were closed
         # (a Hiera-L handle with its AMG scratch is ~58 GB): the same step, the same slices, `--workers` handles; never part of `value`.
         img_prec = eng.prepare(pool[0]).clone()
         for e_ in engines:
@@ -895,7 +925,7 @@ def main():
         except Exception as ex:
             out["alt_dtypes"]["exact"] = {"error": str(ex)[:300]}
         eng = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, weights, img01_cpu, a.crop_n_layers)
     if rank == 0:
         print(json.dumps(out))

@@ -178,9 +178,10 @@ def main():
     out = {k: W[k].detach().float().cpu().numpy() for k in train_keys}
     big = max(float(np.abs(v).max()) for v in out.values())
     assert big < 6.0e4, f"a fitted tensor leaves the fp16 range ({big})"
-    np.savez_compressed(OUT, **{k: v.astype(np.float16) for k, v in out.items()},
-                        __meta__=np.array(f"oracle/fit_decoder_heads.py: {steps} Adam steps x {P} prompts on synthetic_slice(seed 0..{n_slices - 1}), seeded Hiera-L encoder frozen"))
-    print("wrote", OUT, os.path.getsize(OUT), "bytes", flush=True)
+    from saber_amd.utils import npz_parts        # below 1 MiB per file: the archive is written in parts
+    files = npz_parts.save(OUT, dict({k: v.astype(np.float16) for k, v in out.items()},
+                                     __meta__=np.array(f"oracle/fit_decoder_heads.py: {steps} Adam steps x {P} prompts on synthetic_slice(seed 0..{n_slices - 1}), seeded Hiera-L encoder frozen")))
+    print("wrote", files, sum(os.path.getsize(f) for f in files), "bytes", flush=True)
 
 
 if __name__ == "__main__":

@@ -134,8 +134,9 @@ def main():
     c = SAM2AdapterConfig()
     G["adaptercfg_defaults"] = np.array([c.model_type, c.cfg, str(c.checkpoint), str(c.num_maskmem), str(c.light_modality), str(c.min_mask_area)])
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    np.savez_compressed(OUT, **G)
-    print("wrote", OUT, os.path.getsize(OUT), "bytes;", len(G), "arrays")
+    from saber_amd.utils import npz_parts        # below 1 MiB per file: the archive is written in parts
+    files = npz_parts.save(OUT, G)
+    print("wrote", files, sum(os.path.getsize(f) for f in files), "bytes;", len(G), "arrays")
 
 
 if __name__ == "__main__":

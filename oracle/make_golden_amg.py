@@ -62,14 +62,15 @@ def main():
     q = np.zeros((n, 256, 256), dtype=bool)
     for i, a in enumerate(anns):
         q[i] = a["segmentation"][2::4, 2::4]                  # quarter-resolution sample of the full-resolution mask
-    np.savez_compressed(OUT, count=np.array(n), area=np.array([a["area"] for a in anns], dtype=np.int64),
-                        bbox=np.array([a["bbox"] for a in anns], dtype=np.float32).reshape(n, 4),
-                        predicted_iou=np.array([a["predicted_iou"] for a in anns], dtype=np.float32),
-                        stability_score=np.array([a["stability_score"] for a in anns], dtype=np.float32),
-                        point=np.array([a["point_coords"][0] for a in anns], dtype=np.float32).reshape(n, 2),
-                        crop_box=np.array([a["crop_box"] for a in anns], dtype=np.float32).reshape(n, 4),
-                        quarter_bits=np.packbits(q, axis=-1), amg=np.array(repr(AMG)))
-    print("wrote", OUT, os.path.getsize(OUT), "bytes")
+    from saber_amd.utils import npz_parts        # below 1 MiB per file: a larger archive is written in parts
+    files = npz_parts.save(OUT, dict(count=np.array(n), area=np.array([a["area"] for a in anns], dtype=np.int64),
+                                     bbox=np.array([a["bbox"] for a in anns], dtype=np.float32).reshape(n, 4),
+                                     predicted_iou=np.array([a["predicted_iou"] for a in anns], dtype=np.float32),
+                                     stability_score=np.array([a["stability_score"] for a in anns], dtype=np.float32),
+                                     point=np.array([a["point_coords"][0] for a in anns], dtype=np.float32).reshape(n, 2),
+                                     crop_box=np.array([a["crop_box"] for a in anns], dtype=np.float32).reshape(n, 4),
+                                     quarter_bits=np.packbits(q, axis=-1), amg=np.array(repr(AMG))))
+    print("wrote", files, sum(os.path.getsize(f) for f in files), "bytes")
 
 
 if __name__ == "__main__":

@@ -69,8 +69,8 @@ def main():
     G["sem_seg"] = np.stack([np.asarray(m["segmentation"]) for m in sem]).astype(np.uint8)
     G["sem_area"] = np.array([m["area"] for m in sem])
     G["sem_label"] = np.array([m["label"] for m in sem])
-    np.savez_compressed(OUT, **G)
-    print("wrote", OUT, {k: v.shape for k, v in G.items()})
+    from saber_amd.utils import npz_parts        # below 1 MiB per file: the archive is written in parts
+    print("wrote", npz_parts.save(OUT, G), {k: v.shape for k, v in G.items()})
 
 
 if __name__ == "__main__":

@@ -221,14 +221,14 @@ def fitted_decoder_weights(cfg: HieraConfig, seed: int = 0, video: bool = False,
         raise ValueError("the fitted decoder exists for the seeded Hiera-L model (seed 0) only")
     if path is None:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "decoder_fit_large_seed0.npz")
+    from .utils import npz_parts
     W = seeded_weights(cfg, seed, video)
-    with np.load(path) as Z:
-        for k in Z.files:
-            if k.startswith("__"):
-                continue
-            if k not in W or W[k].shape != Z[k].shape:
-                raise ValueError(f"fitted decoder tensor '{k}' does not match the model")
-            W[k] = np.ascontiguousarray(Z[k], dtype=np.float32)
+    for k, v in npz_parts.load(path).items():
+        if k.startswith("__"):
+            continue
+        if k not in W or W[k].shape != v.shape:
+            raise ValueError(f"fitted decoder tensor '{k}' does not match the model")
+        W[k] = np.ascontiguousarray(v, dtype=np.float32)
     return W
 
 

@@ -8,9 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+from saber_amd.utils import npz_parts
+
 pytestmark = pytest.mark.gpu
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "saber_glue.npz"), allow_pickle=False)
+G = npz_parts.load(os.path.join(os.path.dirname(__file__), "golden", "saber_glue.npz"))
 
 
 def run(engine, vol, min_mask_area):

@@ -7,9 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from saber_amd.utils import npz_parts
+
 pytestmark = pytest.mark.gpu
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "saber_classifier_glue.npz"))
+G = npz_parts.load(os.path.join(os.path.dirname(__file__), "golden", "saber_classifier_glue.npz"))
 NC = 3
 
 

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from saber_amd.utils import npz_parts
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-3        # north star: "float logits within 1e-3 rel"
@@ -202,7 +204,7 @@ def test_exact_default_grid_amg_golden(large_weights):
 def _amg_vs_golden(eng, name, amg):
     from oracle import saber_ref
     from saber_amd.engine import make_amg_params, unpack_bits
-    G = np.load(os.path.join(os.path.dirname(__file__), "golden", name))
+    G = npz_parts.load(os.path.join(os.path.dirname(__file__), "golden", name))
     img = eng.prepare(torch.from_numpy(saber_ref.synthetic_slice(seed=0)).cuda())
     bits, meta = eng.amg_generate(img, make_amg_params(amg), max_masks=4096)
     torch.cuda.synchronize()
@@ -219,7 +221,7 @@ def test_exact_default_grid_filters_goldens(large_weights):
     from saber_amd.engine import Engine
     cfg, W = large_weights
     gold = os.path.join(os.path.dirname(__file__), "golden")
-    if not (os.path.exists(os.path.join(gold, "amg_default_grid_stability_seed0.npz")) and os.path.exists(os.path.join(gold, "amg_default_grid_cfgamg_seed0.npz"))):
+    if not (npz_parts.exists(os.path.join(gold, "amg_default_grid_stability_seed0.npz")) and npz_parts.exists(os.path.join(gold, "amg_default_grid_cfgamg_seed0.npz"))):
         pytest.skip("filters goldens not generated (python -m oracle.make_golden_amg with VARIANT=stability / cfgamg: ~40 min of CPU each)")
     eng = Engine("large", device=0, weights=W, max_images=21, max_prompts=1024, precision="exact")
     try:

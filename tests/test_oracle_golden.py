@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "saber_glue.npz"), allow_pickle=False)
+from saber_amd.utils import npz_parts
+
+G = npz_parts.load(os.path.join(os.path.dirname(__file__), "golden", "saber_glue.npz"))
 
 
 def test_oracle_prepare_matches_reference():
@@ -185,7 +187,7 @@ def test_prepare_rgb_restatement_matches_reference_fixture():
 
 # ------------------------------------------------------------------------------------------ classifier filter glue
 def _cls_golden():
-    return np.load(os.path.join(os.path.dirname(__file__), "golden", "saber_classifier_glue.npz"))
+    return npz_parts.load(os.path.join(os.path.dirname(__file__), "golden", "saber_classifier_glue.npz"))
 
 
 def test_classifier_crops_and_preprocess_match_reference():
