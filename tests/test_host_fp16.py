@@ -31,3 +31,15 @@ def test_host_f32_to_f16_matches_numpy(lib):
     o = np.empty(1, dtype=np.uint16)
     lib.saber_k_host_f32_to_f16(nan.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.c_void_p), 1)
     assert np.isnan(o.view(np.float16)[0])
+
+
+def test_video_f16_bits_refuses_a_weight_beyond_the_range():
+    """the video path's fp16 weight conversion (saber_amd.adapters.sam2.video._f16_bits): RNE bit patterns within the range, a loud
+    error beyond 65 504 instead of an inf weight"""
+    import pytest
+    from saber_amd.adapters.sam2.video import _f16_bits
+    a = np.array([[1.0, -65504.0, 2.0 ** -24, 1.0e-3], [3.0e-8, 65503.9, -0.0, 1.0 / 3.0]], dtype=np.float32)
+    assert np.array_equal(_f16_bits(a), a.astype(np.float16).view(np.uint16))
+    for bad in (65504.5, -7.0e4, np.inf):
+        with pytest.raises(ValueError, match="fp16 range"):
+            _f16_bits(np.array([0.5, bad], dtype=np.float32))
