@@ -121,7 +121,9 @@ int saber_get_features(saber_engine* e, int slot, float* image_embed_dev, float*
  * frame's image embedding is replaced by its memory-conditioned version before the mask decoder runs.  Tokens cross this boundary as
  * (4096, 256) fp32 in row-major (y * 64 + x) order.  get: the slot's image_embed (with no_mem_embed, as saber_encode leaves it).
  * set: overwrite it (the slot keeps its high-resolution features).  saber_get_decoder_tokens: the (n, 8, 256) output tokens of the last
- * saber_decode_points call ([obj, iou, mask0..3, point, pad]); upstream projects one mask token to the object pointer. */
+ * saber_decode_points call ([obj, iou, mask0..3, point, pad]); upstream projects one mask token to the object pointer.  After a
+ * saber_decode_prompts call on the 16-token route (saber_engine_set_multipoint) it returns the first 8 of each prompt's token rows
+ * ([obj, iou, mask0..3, point0, point1]) of its last chunk, n <= max_prompts / 2; the mask tokens are rows 2..5 either way. */
 int saber_get_embed_tokens(saber_engine* e, int slot, float* out_tokens_dev, void* stream);
 int saber_set_embed_tokens(saber_engine* e, int slot, const float* tokens_dev, void* stream);
 int saber_get_decoder_tokens(saber_engine* e, int n, float* out_dev, void* stream);
@@ -143,8 +145,9 @@ int saber_decode_points(saber_engine* e, int slot, const float* pts_dev, const i
 /* The same with SEVERAL points per prompt (reference: upstream SAM2's prompt encoder as SAM2VideoPredictor.add_new_points_or_box feeds it -
  * clicks with labels 1 / 0, a box as its two corners with labels 2 / 3 in front of the clicks, label -1 = not a point; one padding point is
  * appended by the engine as upstream does when no box tensor is passed).  pts_dev: (n, points_per_prompt, 2), labels_dev: (n, points_per_prompt).
- * points_per_prompt == 1 is saber_decode_points.  More than one point makes 8 + (points_per_prompt - 1) decoder tokens per prompt: the bf16
- * kernels are built for 8, so such prompts are decoded in the EXACT precision mode only (SABER_ERR_STATE otherwise). */
+ * points_per_prompt == 1 is saber_decode_points.  More than one point makes 8 + (points_per_prompt - 1) decoder tokens per prompt: the 8-token
+ * 16-bit kernels cannot carry them, so such prompts are decoded in the EXACT precision mode, or on the 16-token route of the 16-bit kernels
+ * when saber_engine_set_multipoint is on (SABER_ERR_STATE otherwise). */
 int saber_decode_prompts(saber_engine* e, int slot, const float* pts_dev, const int* labels_dev, int n, int points_per_prompt, int multimask,
                          const float* mask_in_dev, float* out_lowres_dev, float* out_iou_dev, float* out_obj_dev, void* stream);
 
@@ -231,6 +234,12 @@ int saber_engine_set_device_amg(saber_engine* e, int enable);
  * (upstream automatic_mask_generator._process_batch), so its masks are neither upscaled nor read.  saber_amg_last_pruning: how many of the
  * last saber_amg_generate call's m2m candidates were skipped. */
 int saber_engine_set_iou_pruning(saber_engine* e, int enable);
+/* Prompts of 2..9 points (saber_decode_prompts) on the handle's 16-bit kernels (off by default; callable at any time after create): every
+ * prompt carries 16 decoder token rows, rows 7 + points .. 15 are padding that no attention sees, and a call is run in chunks of
+ * max_prompts / 2 prompts in the workspaces of max_prompts 8-token prompts (no extra memory).  0: such prompts need the EXACT precision mode
+ * (SABER_ERR_STATE otherwise).  One point per prompt stays on the 8-token kernels, bit for bit; the EXACT mode ignores the switch.
+ * SABER_ERR_INVALID when enabling it on a handle with max_prompts < 2. */
+int saber_engine_set_multipoint(saber_engine* e, int enable);
 int saber_amg_last_pruning(const saber_engine* e, int64_t* pruned, int64_t* m2m_candidates);
 
 /* plane[y][x] = (position in order_host)+1 of the LAST mask covering the pixel, 0 if none. */

@@ -132,6 +132,12 @@ int saber_k_gemm_batched(const uint16_t* A, int lda, int64_t strideA, const uint
 int saber_k_dec_i2t(const uint16_t* X, int64_t x_batch_stride, const uint16_t* peq, const uint16_t* Kt, const float* tk, float kscale, const float* cb,
                     const uint16_t* VtT, const float* bo, const float* gamma, const float* beta, float eps, uint16_t* Xout, int P, void* stream);
 
+/* saber_k_dec_i2t for prompts of 16 decoder tokens (the 16-token route, saber_engine_set_multipoint): 128 score columns c = 16 h + t, the
+ * softmax over the 16 tokens of each head, columns t >= nvalid (the padding tokens) get exactly zero weight.  Kt [P][128][256] bf16,
+ * tk [P*16][128] f32 (un-folded token keys, positional term kscale * tk_p[16h+t][h] . peq_n[h]), cb [P][128], VtT [P][256][128] bf16. */
+int saber_k_dec_i2t16(const uint16_t* X, int64_t x_batch_stride, const uint16_t* peq, const uint16_t* Kt, const float* tk, float kscale, const float* cb,
+                      const uint16_t* VtT, const float* bo, const float* gamma, const float* beta, float eps, uint16_t* Xout, int P, int nvalid, void* stream);
+
 /* Folded token->image attention (cross_attn_token_to_image / final_attn_token_to_image):
  * out[p][t] = Wv (sum_n softmax_n(Qt_p[h,t].x_n + qscale * tq_p[h,t].pek_n[h]) x_n) + bv.
  * Qt [P][64][256] bf16 (queries folded through W_k), pek = pe W_k^T [4096][128] bf16 (model constant), tq [P*8][128] f32 (un-folded

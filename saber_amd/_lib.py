@@ -74,6 +74,7 @@ SIGNATURES = {
     "saber_amg_generate": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(AmgParams), _vp, _i, C.POINTER(MaskMeta), C.POINTER(_i), _vp]),
     "saber_amg_last_syncs": (_i, [_vp]),
     "saber_engine_set_iou_pruning": (_i, [_vp, _i]),
+    "saber_engine_set_multipoint": (_i, [_vp, _i]),
     "saber_engine_set_device_amg": (_i, [_vp, _i]),
     "saber_amg_last_pruning": (_i, [_vp, _vp, _vp]),
     "saber_engine_set_graphs": (_i, [_vp, _i]),
@@ -115,6 +116,7 @@ SIGNATURES = {
     "saber_k_stream_destroy": (_i, [_vp]),
     "saber_k_host_f32_to_f16": (None, [_vp, _vp, C.c_int64]),
     "saber_k_dec_i2t": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp]),
+    "saber_k_dec_i2t16": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _vp]),
     "saber_k_dec_t2i": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_rope": (_i, [_vp, C.c_int64, _i, _i, _i, _f, _vp, _vp, _vp]),
     "saber_k_softmax_rows": (_i, [_vp, C.c_int64, C.c_int64, _i, _f, _vp, C.c_int64, _vp]),

@@ -29,10 +29,11 @@ def default_precision() -> str:
 
 
 def get_engine(sam2_cfg: str, device, checkpoint: Optional[str] = None, max_images: int = 21, max_prompts: int = 1024, replica: int = 0,
-               precision: Optional[str] = None):
+               precision: Optional[str] = None, multipoint: bool = False):
     """One engine per (device, trunk, weights): the reference builds a second SAM2 copy for AMG (SURVEY 3.4);
     here adapter and generator share one handle.  replica > 0: further handles of the same model on the same device (the z-loop keeps
-    two slices in flight per GPU, one handle per thread)."""
+    two slices in flight per GPU, one handle per thread).  multipoint: the handle decodes box / multi-click prompts on its 16-bit kernels
+    (Engine.set_multipoint; part of the cache key, so the AMG handles of the same model are never switched)."""
     from saber_amd.engine import Engine
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if dev.type != "cuda":
@@ -43,13 +44,13 @@ def get_engine(sam2_cfg: str, device, checkpoint: Optional[str] = None, max_imag
         precision = default_precision()
     if precision not in ("bf16", "fp16"):
         raise ValueError(f"precision must be 'bf16' or 'fp16', got '{precision}'")
-    key = (idx, sam2_cfg, tuple(sorted(src.items())), replica, precision)
+    key = (idx, sam2_cfg, tuple(sorted(src.items())), replica, precision, bool(multipoint))
     if key not in _ENGINES:
         if src.pop("fitted_decoder", None):               # SABER_AMD_SEEDED_WEIGHTS=fitted (tests / bench): seeded encoder + fitted mask decoder
             from saber_amd.model_config import get_config
             from saber_amd.weights import fitted_decoder_weights
             src = {"weights": fitted_decoder_weights(get_config(sam2_cfg), src.get("seed", 0))}
-        eng = Engine(sam2_cfg, device=idx, max_images=max_images, max_prompts=max_prompts, precision=precision, **src)
+        eng = Engine(sam2_cfg, device=idx, max_images=max_images, max_prompts=max_prompts, precision=precision, multipoint=multipoint, **src)
         eng._build = (sam2_cfg, checkpoint)       # what get_replica() needs to build an identical handle
         _ENGINES[key] = eng
     return _ENGINES[key]

@@ -61,8 +61,9 @@ class SAM2Adapter(BaseAdapter):
             from saber_amd import pretrained_weights
             from saber_amd.adapters.sam2.automask import get_engine
             from saber_amd.adapters.sam2.video import VideoPredictor
-            # max_images = frames per batched encoder pass of the tracking loop (VideoPredictor._frame)
-            eng = get_engine(self._config.cfg, self.device, self._config.checkpoint, max_images=16, max_prompts=8, replica=1000)
+            # max_images = frames per batched encoder pass of the tracking loop (VideoPredictor._frame); multipoint: add_new_points_or_box with a
+            # box or several clicks runs on the handle's 16-bit decoder kernels (16-token route)
+            eng = get_engine(self._config.cfg, self.device, self._config.checkpoint, max_images=16, max_prompts=8, replica=1000, multipoint=True)
             W = pretrained_weights.load_weights(self._config.cfg, self._config.checkpoint, video=True)
             self._video_predictor = VideoPredictor(eng, W, num_maskmem=self._config.num_maskmem)
         return self._video_predictor
@@ -87,8 +88,8 @@ class SAM2Adapter(BaseAdapter):
     def add_new_points_or_box(self, frame_idx: int, obj_id: int, inference_state=None, **kwargs) -> Tuple:
         """predictor.py:171-180: delegates to the video predictor (points=, labels=, clear_old_points=, normalize_coords=, box=).  Clicks,
         several clicks per call, boxes and corrections of tracked frames follow upstream (adapters/sam2/video.py); prompts of more than one
-        point are decoded in the engine's exact precision mode, which the handle must have been created with (NotImplementedError says so
-        otherwise).  No SABER caller uses them: segmenters/base.py:265-280 seeds propagation with masks."""
+        point are decoded on the handle's 16-bit kernels (the 16-token route: _video() builds its handle with multipoint on).  No SABER
+        caller uses them: segmenters/base.py:265-280 seeds propagation with masks."""
         state = inference_state or self.inference_state
         if state is None:
             raise RuntimeError("Call set_volume() before add_new_points_or_box().")

@@ -366,21 +366,27 @@ class VideoPredictor:
                    point: Optional[Tuple[float, float]] = None, label: int = -1, points=None, labels=None):
         """returns (low (256,256) device fp32, obj logit float, obj_ptr (1,256) device fp32); slot: the engine slot that holds the frame;
         point / label: one click in the model's 1024-px frame (None: upstream's padding point with label -1); points (k,2) / labels (k,),
-        k > 1: several clicks / a box's corners - decoded in the engine's exact precision mode (saber_decode_prompts), which the handle must
-        have been created with (Engine(..., precision="exact"); the production precision is restored afterwards)"""
+        k > 1: several clicks / a box's corners (saber_decode_prompts) - on the handle's 16-bit kernels when it has multipoint on
+        (Engine(..., multipoint=True): the 16-token route, no precision switch), else in the engine's exact precision mode, which the handle
+        must then have been created with (Engine(..., precision="exact"); the production precision is restored afterwards)"""
         self.eng._check(self.lib.saber_set_embed_tokens(self.eng.h, slot, self._p(embed_tokens), self._s()))
         if points is not None and len(points) > 1:
             was = self.eng.precision
-            if not getattr(self.eng, "has_exact", was == "exact"):
-                raise NotImplementedError("several points / a box per prompt make more than 8 decoder tokens: they are decoded in the exact precision mode - "
-                                          "create the Engine with precision='exact' (it can run in bf16 between such calls: Engine.set_precision)")
+            multipoint = getattr(self.eng, "multipoint", False)
+            if not multipoint and not getattr(self.eng, "has_exact", was == "exact"):
+                raise NotImplementedError("several points / a box per prompt make more than 8 decoder tokens: they are decoded on the 16-bit kernels' "
+                                          "16-token route (Engine(..., multipoint=True)) or in the exact precision mode (Engine(..., precision='exact'); "
+                                          "it can run in bf16 between such calls: Engine.set_precision)")
             pts = torch.as_tensor(np.asarray(points, np.float32).reshape(1, -1, 2)).to(self.dev)
             lab = torch.as_tensor(np.asarray(labels, np.int32).reshape(1, -1)).to(self.dev)
-            self.eng.set_precision("exact")
-            try:
+            if multipoint:
                 low, iou, obj = self.eng.decode_prompts(pts, lab, slot=slot, multimask=multimask, mask_input=mask_in)
-            finally:
-                self.eng.set_precision(was)
+            else:
+                self.eng.set_precision("exact")
+                try:
+                    low, iou, obj = self.eng.decode_prompts(pts, lab, slot=slot, multimask=multimask, mask_input=mask_in)
+                finally:
+                    self.eng.set_precision(was)
         else:
             if points is not None and len(points) == 1:
                 point, label = (float(points[0][0]), float(points[0][1])), int(labels[0])

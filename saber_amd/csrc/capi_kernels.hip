@@ -25,6 +25,7 @@ extern "C" int saber_k_init(int device_id) {
     if (!m) m = hiera_attention_init_device();
     if (!m) m = image_ops_init_device();
     if (!m) m = decoder_fused_init_device();
+    if (!m) m = decoder_t16_init_device();
     if (!m) m = amg_device_init();
     (void)hipGetLastError();
     if (m) return kfail(m);
@@ -122,6 +123,12 @@ extern "C" int saber_k_dec_i2t(const uint16_t* X, int64_t x_batch_stride, const 
                                const uint16_t* VtT, const float* bo, const float* gamma, const float* beta, float eps, uint16_t* Xout, int P,
                                void* stream) {
     return kcheck(launch_dec_i2t(X, XMap{x_batch_stride, 1, 0}, peq, Kt, tk, kscale, cb, VtT, bo, gamma, beta, eps, Xout, P, (hipStream_t)stream));
+}
+
+extern "C" int saber_k_dec_i2t16(const uint16_t* X, int64_t x_batch_stride, const uint16_t* peq, const uint16_t* Kt, const float* tk, float kscale, const float* cb,
+                                 const uint16_t* VtT, const float* bo, const float* gamma, const float* beta, float eps, uint16_t* Xout, int P, int nvalid,
+                                 void* stream) {
+    return kcheck(launch_dec_i2t16(X, XMap{x_batch_stride, 1, 0}, peq, Kt, tk, kscale, cb, VtT, bo, gamma, beta, eps, Xout, P, nvalid, (hipStream_t)stream));
 }
 
 extern "C" int saber_k_dec_t2i(const uint16_t* X, int64_t x_batch_stride, const uint16_t* pek, const uint16_t* Qt, const float* tq, float qscale, float* part_ws,

@@ -89,7 +89,9 @@ struct saber_engine {
     unsigned long long* prune_counters = nullptr;   // device: [0] pruned, [1] seen (accumulated by iou_live_flags_kernel)
     unsigned int* nonfinite = nullptr;              // device: overflow-sentinel counters (engine.hip "sentinel"); the 16 bytes behind prune_counters[0..1]
     int64_t amg_last_pruned = 0, amg_last_m2m = 0;    // statistics of the last saber_amg_generate call (bench.py)
-    int decode_n_pts = 1;           // points per prompt of the decode call in progress (saber_decode_prompts; exact precision only when > 1)
+    int decode_n_pts = 1;           // points per prompt of the decode call in progress (saber_decode_prompts; exact precision or multipoint when > 1)
+    bool multipoint = false;        // saber_engine_set_multipoint: prompts of 2..9 points on the 16-bit kernels (decoder_t16.hip, 16 token rows per prompt)
+    int dec_tok_rows = 8;           // token rows per prompt that the last decode left in `queries` (16 after the 16-token route)
     uint8_t *xn8_s = nullptr, *hid8_s = nullptr; int64_t mx_rows = 0;   // MXFP8 weight format: scale panels of the MX activations (their e4m3 bytes reuse xn / hid); mx_rows = panel rows
     bf16_t* sb[4] = {nullptr, nullptr, nullptr, nullptr};
     int* crops_dev = nullptr;

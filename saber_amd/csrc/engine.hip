@@ -160,6 +160,12 @@ extern "C" int saber_engine_set_iou_pruning(saber_engine* e, int enable) {
     if ((bool)enable != e->iou_prune) { e->iou_prune = enable != 0; eng_graphs_flush(e); }      // (captured decode sequences contain the choice)
     return SABER_OK;
 }
+extern "C" int saber_engine_set_multipoint(saber_engine* e, int enable) {
+    if (!e) return SABER_ERR_INVALID;
+    if (enable && e->max_prompts < 2) return eng_fail(e, SABER_ERR_INVALID, "set_multipoint: the 16-token route needs max_prompts >= 2 (chunks of max_prompts / 2 prompts)");
+    e->multipoint = enable != 0;
+    return SABER_OK;
+}
 extern "C" int saber_engine_set_encoder_stream(saber_engine* e, void* stream) {
     if (!e) return SABER_ERR_INVALID;
     if ((hipStream_t)stream != e->enc_stream) { eng_graphs_flush(e); e->enc_stream = (hipStream_t)stream; }     // (captured encoder passes belong to their stream)
@@ -207,6 +213,7 @@ extern "C" int saber_engine_create(int device_id, const char* trunk, int max_ima
         if (!m) m = image_ops_init_device();
         if (!m) m = decoder_fused_init_device();
         if (!m) m = decoder_tokens_init_device();
+        if (!m) m = decoder_t16_init_device();
         (void)hipGetLastError();
         if (m) { delete e; return eng_fail(nullptr, SABER_ERR_HIP, std::string("kernel attribute setup: ") + m); }
     }
@@ -1208,13 +1215,19 @@ extern "C" int saber_import_slots(saber_engine* e, int slot0, int n, const float
     return SABER_OK;
 }
 // the 8 tokens of the first n prompts of the LAST decode call after the two-way transformer ([obj, iou, mask0..3, point, pad] x 256 fp32):
-// the video path projects one mask token to the object pointer (upstream obj_ptr_proj(sam_output_token))
+// the video path projects one mask token to the object pointer (upstream obj_ptr_proj(sam_output_token)).  After a decode on the 16-token route
+// (saber_engine_set_multipoint) the first 8 of each prompt's 16 rows: [obj, iou, mask0..3, point0, point1]
 extern "C" int saber_get_decoder_tokens(saber_engine* e, int n, float* out_dev, void* stream) {
     if (!e) return SABER_ERR_INVALID;
     if (!e->finalized) return eng_fail(e, SABER_ERR_STATE, "engine not finalized");
     if (n < 1 || n > e->max_prompts || !out_dev) return eng_fail(e, SABER_ERR_INVALID, "get_decoder_tokens: n must be 1..max_prompts");
     ENG_DEVICE(e);
-    ENG_HIP(e, hipMemcpyAsync(out_dev, e->queries, sizeof(float) * (size_t)n * 8 * 256, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (e->dec_tok_rows == 16) {
+        if (2 * n > e->max_prompts) return eng_fail(e, SABER_ERR_INVALID, "get_decoder_tokens: after a 16-token decode n must be 1..max_prompts / 2");
+        for (int p = 0; p < n; ++p)
+            ENG_HIP(e, hipMemcpyAsync(out_dev + (size_t)p * 8 * 256, e->queries + (size_t)p * 16 * 256, sizeof(float) * 8 * 256, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    } else
+        ENG_HIP(e, hipMemcpyAsync(out_dev, e->queries, sizeof(float) * (size_t)n * 8 * 256, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return SABER_OK;
 }
 
@@ -1237,6 +1250,106 @@ static int ensure_embb(saber_engine* e, int slot, hipStream_t s) {
     return SABER_OK;
 }
 
+// One chunk of P prompts of K = e->decode_n_pts (2..9) points each on the 16-token route (decoder_t16.hip; saber_engine_set_multipoint): every
+// prompt carries 16 token rows, 7 + K of them real.  The token workspaces sized for max_prompts x 8 rows at finalize hold P <= max_prompts / 2
+// prompts of 16 rows; fold_q / t2i_part / t2i_ml hold the 2P half prompts of the tokens -> image attentions.  Always the fused token side and
+// a materialised X for layer 0 of a mask-prompted decode (no SABER_AMD_NO_TOKFUSE / SABER_AMD_XBUILD / SABER_AMD_FUSE_I2T_T2I variants).
+static int decode_chunk16(saber_engine* e, int slot0, int per_slot, int p_base, const float* pts, const int* labels, int P, int multimask,
+                          const float* mask_in, float mask_clamp, float* out_lowres, float* out_iou, float* out_obj, hipStream_t s,
+                          float* raw4_out, int* out_sel, int mask_in_q0, float prune_iou_thr) {
+    const int K = e->decode_n_pts, nvalid = 7 + K;
+    if (K < 2 || K > 9) return eng_fail(e, SABER_ERR_INVALID, "decode: the 16-token route takes 2..9 points per prompt");
+    if (2 * P > e->max_prompts) return eng_fail(e, SABER_ERR_INVALID, "decode: a 16-token chunk holds at most max_prompts / 2 prompts");
+    const int PT = P * 16;
+    const size_t o256 = (size_t)slot0 * 4096 * 256;
+    const int slot_last = slot0 + (p_base + P - 1) / per_slot;
+    const XMap slots{(int64_t)4096 * 256, per_slot, p_base};
+    const XMap per_prompt{(int64_t)4096 * 256, 1, 0};
+    auto halves = [](XMap m) { return XMap{m.stride, 2 * m.div, 2 * m.off}; };    // half prompt v reads the image tokens of prompt v / 2
+    const float kScale = 0.25f * 1.4426950408889634f;
+    int split = 1;
+    while (split < 8 && 2 * P * split < 512) split *= 2;
+    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_prompt_tokens16(pts, labels, P, K, e->pw, e->tok_pe, s));
+    ENG_HIP(e, hipMemcpyAsync(e->queries, e->tok_pe, sizeof(float) * PT * 256, hipMemcpyDeviceToDevice, s));
+    e->dec_tok_rows = 16;
+    const bf16_t* X;
+    XMap xm;
+    if (mask_in == nullptr) {
+        for (int sl = slot0 + p_base / per_slot; sl <= slot_last; ++sl) TRY(ensure_shared(e, sl, s));
+        X = e->src0_bf + o256; xm = slots;
+    } else {
+        ENG_KP(e, PC_ELEMENTWISE, 0.0, (double)P * (65536.0 * 4 + 4096.0 * 256 * 2), launch_mask_embed_src(mask_in, P, e->emb + o256, slots, e->dense_pe, e->mw, nullptr, e->keys_bf, nullptr, mask_clamp, s, mask_in_q0));
+        X = e->keys_bf; xm = per_prompt;
+    }
+    auto lin = [](const LinW& l) { TokLin t; t.w = l.w; t.b = l.b; t.ldw = l.ldw; t.n = l.out; t.wpk = l.wpk; t.npk = l.wpk_n; return t; };
+    auto lnw = [](const LnW& l) { TokLn t; t.g = l.g; t.b = l.b; return t; };
+    auto base = [&]() { TokSeg g; g.P = P; g.queries = e->queries; g.tok_pe = e->tok_pe; g.kscale = kScale; return g; };
+    auto with_t2i = [&](TokSeg& g, const AttnW& a) { g.do_t2i = 1; g.t2i_q = lin(a.q); g.t2i_kT = a.img_wT; g.tq_out = e->tq; g.fold_q = e->fold_q; };
+    auto with_self = [&](TokSeg& g, const DecLayerW& w, int first) {
+        g.do_self = 1; g.self_first = first; g.sa_q = lin(w.self_attn.q); g.sa_k = lin(w.self_attn.k); g.sa_v = lin(w.self_attn.v); g.sa_o = lin(w.self_attn.o); g.ln1 = lnw(w.n1);
+    };
+    auto with_att_out = [&](TokSeg& g, const AttnW& a, const LnW& ln) { g.t_att = e->t_att; g.att_o = lin(a.o); g.att_ln = lnw(ln); g.att_eps = 1e-5f; };
+    auto with_mlp_i2t = [&](TokSeg& g, const DecLayerW& w) {
+        g.do_mlp = 1; g.mlp1 = lin(w.mlp1); g.mlp2 = lin(w.mlp2); g.mlp1_pk = w.mlp1.wpk; g.mlp2_pk = w.mlp2.wpk; g.ln3 = lnw(w.n3);
+        g.i2t_k = lin(w.i2t.k); g.i2t_v = lin(w.i2t.v); g.i2t_qT = w.i2t.img_wT; g.i2t_qb = w.i2t.q.b; g.i2t_o = w.i2t.o.w;
+        g.tk_out = e->tk; g.fold_k = e->fold_k; g.fold_cb = e->fold_cb; g.fold_v = e->fold_v;
+    };
+    const double tflops = 2.0 * PT * 256.0;
+    auto run_t2i = [&](const AttnW& a) -> int {
+        ENG_KP(e, PC_DEC_T2I, 4.0 * 128 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 4, launch_dec_t2i(X, halves(xm), a.pe_proj, e->fold_q, e->tq, kScale, e->t2i_part, e->t2i_ml, 2 * P, split, a.v.w, a.v.b, e->t_att, s));
+        return SABER_OK;
+    };
+    auto run_i2t = [&](const DecLayerW& w) -> int {
+        ENG_KP(e, PC_DEC_I2T, 4.0 * 128 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 4, launch_dec_i2t16(X, xm, w.i2t.pe_proj, e->fold_k, e->tk, kScale, e->fold_cb, e->fold_v, w.i2t.o.b, w.n4.g, w.n4.b, 1e-5f, e->keys_bf, P, nvalid, s));
+        X = e->keys_bf; xm = per_prompt;
+        return SABER_OK;
+    };
+    {   // S0: self attention of layer 0, operands of its tokens -> image attention
+        TokSeg g = base(); with_self(g, e->dl[0], 1); with_t2i(g, e->dl[0].t2i);
+        ENG_KP(e, PC_DEC_ATTN, tflops * (4 * 256 + 128 + 128), 0.0, launch_dec_tokens16(g, nvalid, s));
+    }
+    TRY(run_t2i(e->dl[0].t2i));
+    {   // S1: rest of layer 0, self attention of layer 1, operands of its tokens -> image attention
+        TokSeg g = base(); with_att_out(g, e->dl[0].t2i, e->dl[0].n2); with_mlp_i2t(g, e->dl[0]); with_self(g, e->dl[1], 0); with_t2i(g, e->dl[1].t2i);
+        ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 4096 + 4 * 128 + 4 * 256 + 256), 0.0, launch_dec_tokens16(g, nvalid, s));
+    }
+    TRY(run_i2t(e->dl[0]));
+    TRY(run_t2i(e->dl[1].t2i));
+    {   // S2: rest of layer 1, operands of the final tokens -> image attention
+        TokSeg g = base(); with_att_out(g, e->dl[1].t2i, e->dl[1].n2); with_mlp_i2t(g, e->dl[1]); with_t2i(g, e->final_attn);
+        ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 4096 + 4 * 128 + 256), 0.0, launch_dec_tokens16(g, nvalid, s));
+    }
+    TRY(run_i2t(e->dl[1]));
+    TRY(run_t2i(e->final_attn));
+    {   // S3: final output projection + LayerNorm, IoU / object-score / hypernetwork heads
+        TokSeg g = base(); with_att_out(g, e->final_attn, e->final_ln);
+        g.do_heads = 1;
+        for (int l = 0; l < 3; ++l) { g.iou[l] = lin(e->iou_head[l]); g.obj[l] = lin(e->obj_head[l]); g.hyper[l] = lin(e->hyper[l]); }
+        g.iou4 = e->iou4; g.obj_out = out_obj; g.hyper_out = e->hyper_out;
+        ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 6 * 512.0 / 16), 0.0, launch_dec_tokens16(g, nvalid, s));
+    }
+    // overflow sentinel, IoU pruning, upscaling and mask selection as on the 8-token route (per prompt: independent of the token count)
+    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_nonfinite_scan(e->iou4, (int64_t)P * 4, e->nonfinite + 1, s));
+    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_nonfinite_scan(e->hyper_out, (int64_t)P * 128, e->nonfinite + 1, s));
+    const uint8_t* live = nullptr;
+    if (prune_iou_thr > 0.f && raw4_out && !multimask && e->iou_prune) {
+        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_iou_live_flags(e->iou4, P, prune_iou_thr, e->live, e->prune_counters, s));
+        live = e->live;
+    }
+    ENG_KP(e, PC_DEC_UPSCALE, (double)P * 2.0 * (4096.0 * 256 * 256 + 16384.0 * 64 * 128 + 65536.0 * 32 * 4), (double)P * (4096.0 * 256 * 2 + 4 * 65536.0 * 4),
+           launch_dec_upscale(X, e->dc1.w, e->dc1.b, e->up_ln.g, e->up_ln.b, e->dc2p, e->dc2.b, e->fs1 + (size_t)slot0 * 16384 * 64,
+                              e->fs0 + (size_t)slot0 * 65536 * 32, XMap{0, per_slot, p_base}, e->hyper_out, raw4_out ? raw4_out : e->masks4, P, s, live,
+                              e->iou4, multimask, e->nonfinite + 2));
+    float* oi = out_iou ? out_iou : e->dec_out_iou;
+    if (raw4_out) {
+        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_pick(raw4_out, e->iou4, P, multimask, oi, out_sel, s, live));
+        return SABER_OK;
+    }
+    float* om = out_lowres ? out_lowres : e->dec_out_masks;
+    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_select(e->masks4, e->iou4, P, multimask, om, oi, e->counts_ws, s));
+    return SABER_OK;
+}
+
 // One chunk of P prompts.  The prompts may span several consecutive slots (crops of one AMG layer batched together): prompt p of
 // the chunk reads the features of slot slot0 + (p_base + p) / per_slot.
 // raw4_out: the chunk's 4 low-res planes per prompt are written there and stay (no selection copy: out_iou / out_sel say which to read);
@@ -1253,7 +1366,12 @@ static int decode_chunk(saber_engine* e, int slot0, int per_slot, int p_base, co
         ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_select(e->masks4, e->iou4, P, multimask, om, oi, e->counts_ws, s));
         return SABER_OK;
     }
-    if (e->decode_n_pts != 1) return eng_fail(e, SABER_ERR_STATE, "prompts of several points (clicks, boxes) are decoded in the exact precision mode only: the bf16 kernels are built for 8 decoder tokens per prompt");
+    if (e->decode_n_pts != 1) {
+        if (e->multipoint)
+            return decode_chunk16(e, slot0, per_slot, p_base, pts, labels, P, multimask, mask_in, mask_clamp, out_lowres, out_iou, out_obj, s, raw4_out, out_sel,
+                                  mask_in_q0, prune_iou_thr);
+        return eng_fail(e, SABER_ERR_STATE, "prompts of several points (clicks, boxes) are decoded in the exact precision mode only: the bf16 kernels are built for 8 decoder tokens per prompt");
+    }
     const int T = 8;
     const int PT = P * T;
     const size_t o256 = (size_t)slot0 * 4096 * 256;
@@ -1467,7 +1585,10 @@ int eng_decode_ex(saber_engine* e, int slot, int per_slot, const float* pts_dev,
         if (sl < 0 || sl >= e->max_images || !e->slot_valid[sl]) return eng_fail(e, SABER_ERR_STATE, "decode: slot holds no encoded image; call saber_encode first");
     const int M = multimask ? 3 : 1;
     const int K = e->decode_n_pts;                  // points per prompt (1 except under saber_decode_prompts)
-    const int chunk = e->precision == SABER_PRECISION_EXACT ? std::max(1, exact_chunk_prompts(e) * 8 / (7 + K)) : e->max_prompts;
+    const int chunk = e->precision == SABER_PRECISION_EXACT ? std::max(1, exact_chunk_prompts(e) * 8 / (7 + K))
+                      : K > 1 && e->multipoint ? std::max(1, e->max_prompts / 2)        // 16-token route: 16 rows per prompt in workspaces of max_prompts x 8
+                                               : e->max_prompts;
+    e->dec_tok_rows = 8;
     for (int p0 = 0; p0 < n; p0 += chunk) {
         const int P = std::min(chunk, n - p0);
         const float* min_ = !mask_in_dev ? nullptr : mask_in_raw4 ? mask_in_dev : mask_in_dev + (size_t)p0 * 65536;

@@ -70,6 +70,16 @@ const char* launch_dec_upscale(const bf16_t* X, const bf16_t* W1, const float* b
 const char* decoder_fused_init_device();
 const char* launch_dec_tokens(const TokSeg& s, hipStream_t st);
 const char* decoder_tokens_init_device();
+// ------------------------------------------------------------------ decoder_t16.hip: the 16-token route (prompts of 2..9 points)
+// tokens [P][16][256] fp32 = [obj, iou, mask0..3, K points, padding point, zero rows]
+const char* launch_prompt_tokens16(const float* pts, const int* labels, int P, int K, PromptWeights w, float* tokens, hipStream_t s);
+// dec_tokens for 16 token rows per prompt (nvalid = 7 + K of them are attention keys).  Fold layouts: fold_q [P][2][64][256] (two half prompts
+// of 8 tokens for launch_dec_t2i with 2P prompts), fold_k [P][128][256] (c = 16 h + t), fold_cb [P][128], fold_v [P][256][128]; tq / tk / t_att [P * 16][128]
+const char* launch_dec_tokens16(const TokSeg& s, int nvalid, hipStream_t st);
+// dec_i2t with 16 tokens per prompt: Kt [P][128][256], tk [P * 16][128], cb [P][128], VtT [P][256][128]; score columns t >= nvalid get zero weight
+const char* launch_dec_i2t16(const bf16_t* X, XMap xm, const bf16_t* peq, const bf16_t* Kt, const float* tk, float kscale, const float* cb, const bf16_t* VtT,
+                             const float* bo, const float* gamma, const float* beta, float eps, bf16_t* Xout, int P, int nvalid, hipStream_t s);
+const char* decoder_t16_init_device();
 const char* launch_mask_post(const float* lowres, const int* idx, int n, int crop_x0, int crop_y0, int crop_w, int crop_h, int H,
                              int W, float thr, float offset, uint32_t* bits, MaskStats* stats, hipStream_t s, const uint8_t* pass = nullptr);   // pass: optional per-mask flags, masks with 0 are skipped
 // paint label planes: plane[y][x] = max over i (in order) ... later masks overwrite earlier ones (propagation.py:185-186)

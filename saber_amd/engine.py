@@ -31,7 +31,7 @@ class Engine:
 
     def __init__(self, trunk: str = "large", device: int = 0, weights: Optional[Dict[str, np.ndarray]] = None,
                  checkpoint: Optional[str] = None, seed: int = 0, max_images: int = 1, max_prompts: int = 64, weight_format: str = "bf16", precision: str = "bf16",
-                 operands: Optional[str] = None):
+                 operands: Optional[str] = None, multipoint: bool = False):
         self.lib = _lib.load()
         self.cfg = get_config(trunk)  # ValueError for unknown names, like the reference
         if not torch.cuda.is_available():
@@ -66,6 +66,9 @@ class Engine:
             self._check(self.lib.saber_engine_set_precision(self.h, 2))
         if precision == "exact":         # fp32 operands everywhere (include/saber_amd.h: saber_engine_set_precision); keeps fp32 weight copies
             self._check(self.lib.saber_engine_set_precision(self.h, 1))
+        self.multipoint = False
+        if multipoint:
+            self.set_multipoint(True)
         if weights is None:
             weights = load_checkpoint(checkpoint, self.cfg) if checkpoint else seeded_weights(self.cfg, seed)
         for name, arr in weights.items():
@@ -91,6 +94,7 @@ class Engine:
         self.h = h
         self.cfg = None
         self.max_images = self.max_prompts = 0
+        self.multipoint = False
         return self
 
     def _check(self, st: int):
@@ -179,8 +183,9 @@ class Engine:
 
     def decode_prompts(self, pts: torch.Tensor, labels: torch.Tensor, slot: int = 0, multimask: bool = False, mask_input: Optional[torch.Tensor] = None):
         """Prompts of several points each (clicks with labels 1 / 0; a box = its two corners with labels 2 / 3 first; -1 = not a point).
-        pts: (n,k,2) float32 model-pixel coords, labels: (n,k) int32, both on the device.  With k > 1 the handle must be in the exact
-        precision mode (the bf16 decoder kernels carry 8 tokens per prompt).  Returns (lowres (n,M,256,256), iou (n,M), obj (n,))."""
+        pts: (n,k,2) float32 model-pixel coords, labels: (n,k) int32, both on the device, k = 1..9.  With k > 1 the handle must be in the
+        exact precision mode, or have multipoint on (set_multipoint: the 16-token route of the 16-bit decoder kernels, chunks of
+        max_prompts / 2 prompts); otherwise RuntimeError.  Returns (lowres (n,M,256,256), iou (n,M), obj (n,))."""
         assert pts.is_cuda and pts.dtype == torch.float32 and pts.is_contiguous() and pts.dim() == 3 and pts.shape[2] == 2
         n, k = pts.shape[:2]
         assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (n, k)
@@ -284,6 +289,12 @@ class Engine:
     def set_iou_pruning(self, enable: bool):
         """IoU pruning of the AMG m2m pass (include/saber_amd.h: saber_engine_set_iou_pruning); on by default, results identical."""
         self._check(self.lib.saber_engine_set_iou_pruning(self.h, int(bool(enable))))
+
+    def set_multipoint(self, enable: bool):
+        """Prompts of 2..9 points (decode_prompts) on the handle's 16-bit kernels: the 16-token route (include/saber_amd.h:
+        saber_engine_set_multipoint); off by default, where such prompts need the exact precision mode.  ValueError with max_prompts < 2."""
+        self._check(self.lib.saber_engine_set_multipoint(self.h, int(bool(enable))))
+        self.multipoint = bool(enable)
 
     def last_pruning(self):
         """(m2m candidates skipped, m2m candidates) of the last amg_generate call"""
