@@ -145,6 +145,37 @@ int saber_k_dec_i2t16(const uint16_t* X, int64_t x_batch_stride, const uint16_t*
 int saber_k_dec_t2i(const uint16_t* X, int64_t x_batch_stride, const uint16_t* pek, const uint16_t* Qt, const float* tq, float qscale, float* part_ws,
                     float* ml_ws, int P, int split, const uint16_t* Wv, const float* bv, uint16_t* out, void* stream);
 
+/* Head of the mask decoder (reference: sam2/modeling/sam/mask_decoder.py MaskDecoder.predict_masks, everything after the two-way transformer:
+ * output_upscaling with the high-resolution features + the hypernetwork product), one fused kernel (csrc/decoder_fused.hip dec_upscale_kernel):
+ *   u1 = GELU(LN2d_64(ConvT_k2s2(x; w0, b0) + feat_s1));  u2 = GELU(ConvT_k2s2(u1; w3, b3) + feat_s0);  masks4[p][k][y][x] = sum_c hyper[p][k][c] u2[c][y][x]
+ * (LayerNorm over the 64 channels, eps 1e-6, biased variance; exact-erf GELU evaluated by a fitted form, |error| <= 2.6e-5 absolute).
+ * X [P][4096][256] 16-bit: the transformer's image tokens, row saber_k_perm_index(y, x, 2) = token (y, x) of the 64 x 64 grid.
+ * w0 = output_upscaling.0.weight [256][64][2][2], b0 [64], w3 = output_upscaling.3.weight [64][32][2][2], b3 [32]: fp32 in checkpoint layout (device or
+ * host pointers); they are packed by the function saber_engine_finalize packs them with and rounded to the operand type.  ln_gamma / ln_beta [64] f32.
+ * fs1 [slots][16384][64], fs0 [slots][65536][32] f32: the high-resolution features channels-last, row saber_k_perm_index(y, x, 1) / (y, x, 0) of the
+ * 128 / 256 grid; prompt p reads slot (p + slot_off) / slot_div (slot_div > 0, slot_off >= 0; the caller provides (P - 1 + slot_off) / slot_div + 1 slots).
+ * hyper [P][4][32] f32; masks4 [P][4][256][256] f32 out, row-major pixels.
+ * 16-bit roundings: X, w0, w3 as given; u1 (the B operand of the second ConvT's MFMA) and u2 (the B operand of the hypernetwork MFMA) are rounded to
+ * the operand type; hyper enters as a hi + lo pair of that type (not rounded); everything else is fp32.
+ * live (optional, [P] bytes): prompts whose flag is 0 are skipped, their four planes are not written.  iou4 (optional, [P][4] f32): only the planes a
+ * selection can return are written - multimask: planes 1-3; single mask: plane 0 and plane 1 + (first maximum of iou4[p][1..3], the rule of
+ * saber_k_mask_pick / saber_k_mask_select; a NaN never wins a comparison).  sentinel (optional): incremented when a stored logit is NaN / inf, by the
+ * number of lanes of the storing waves whose sticky flag is set (> 0 = something overflowed; not a count of pixels).
+ * The call packs the weights into a temporary and returns after the launch has completed (it synchronises the stream; not capturable). */
+int saber_k_dec_upscale(const uint16_t* X, const float* w0, const float* b0, const float* ln_gamma, const float* ln_beta, const float* w3, const float* b3,
+                        const float* fs1, const float* fs0, int slot_div, int slot_off, const float* hyper, float* masks4, int P, const uint8_t* live,
+                        const float* iou4, int multimask, unsigned int* sentinel, void* stream);
+/* The selection among the four planes (reference: MaskDecoder.forward / _dynamic_multimask_via_stability, delta 0.05, threshold 0.98), fp32:
+ * multimask: out_iou [P][3] = iou4[:, 1:], out_sel untouched.  Single mask: stability = #(plane 0 > 0.05) / #(plane 0 > -0.05) in fp32 (1 when the
+ * denominator is 0); stable (>= 0.98f): plane 0, else 1 + first maximum of iou4[p][1..3]; out_iou [P] = iou4 of the chosen plane, out_sel [P]
+ * (may be NULL) = its index.  live (optional): prompts with flag 0 report plane 0 and iou4[p][0] without reading their planes. */
+int saber_k_mask_pick(const float* masks4, const float* iou4, int P, int multimask, float* out_iou, int* out_sel, const uint8_t* live, void* stream);
+/* the same selection with the copy: out_masks [P][3][256][256] = planes 1-3 (multimask) or [P][256][256] = the chosen plane; out_iou as above */
+int saber_k_mask_select(const float* masks4, const float* iou4, int P, int multimask, float* out_masks, float* out_iou, void* stream);
+/* live[p] = any of iou4[p][0..3] > thr (strict): whether a single-mask candidate can pass a `predicted IoU > thr` filter at all.
+ * counters (optional, 2 x uint64): [0] += prompts with flag 0, [1] += P */
+int saber_k_iou_live_flags(const float* iou4, int P, float thr, uint8_t* live, unsigned long long* counters, void* stream);
+
 /* Development (co-residency experiments, tools/cu_mask_bench.py): a HIP stream restricted to CUs first_cu .. first_cu + n_cus - 1
  * (hipExtStreamCreateWithCUMask), and its release. */
 int saber_k_stream_create_cu_range(int first_cu, int n_cus, void** out_stream);

@@ -118,6 +118,10 @@ SIGNATURES = {
     "saber_k_dec_i2t": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp]),
     "saber_k_dec_i2t16": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _vp]),
     "saber_k_dec_t2i": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "saber_k_dec_upscale": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "saber_k_mask_pick": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "saber_k_mask_select": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "saber_k_iou_live_flags": (_i, [_vp, _i, _f, _vp, _vp, _vp]),
     "saber_k_rope": (_i, [_vp, C.c_int64, _i, _i, _i, _f, _vp, _vp, _vp]),
     "saber_k_softmax_rows": (_i, [_vp, C.c_int64, C.c_int64, _i, _f, _vp, C.c_int64, _vp]),
     "saber_k_conv3x3s2": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),

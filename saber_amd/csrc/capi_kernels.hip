@@ -1,9 +1,13 @@
 // Kernel-level C-ABI (include/saber_amd_kernels.h): thin wrappers over the launchers.
+#include <cmath>
+#include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/saber_amd_kernels.h"
 #include "common.h"
 #include "kernels.h"
+#include "engine.h"
 
 #include <atomic>
 
@@ -134,6 +138,70 @@ extern "C" int saber_k_dec_i2t16(const uint16_t* X, int64_t x_batch_stride, cons
 extern "C" int saber_k_dec_t2i(const uint16_t* X, int64_t x_batch_stride, const uint16_t* pek, const uint16_t* Qt, const float* tq, float qscale, float* part_ws,
                                float* ml_ws, int P, int split, const uint16_t* Wv, const float* bv, uint16_t* out, void* stream) {
     return kcheck(launch_dec_t2i(X, XMap{x_batch_stride, 1, 0}, pek, Qt, tq, qscale, part_ws, ml_ws, P, split, Wv, bv, out, (hipStream_t)stream));
+}
+
+// ------------------------------------------------------------------------------------------------ head of the mask decoder
+// The ConvTranspose weights arrive in checkpoint layout and go through the packer saber_engine_finalize uses (saber_pack_upscale, engine.hip).
+// They are packed once per call into one device temporary that is released after the launch has completed: the call returns with the
+// stream drained (no scratch kept per thread or per device).
+extern "C" int saber_k_dec_upscale(const uint16_t* X, const float* w0, const float* b0, const float* ln_gamma, const float* ln_beta, const float* w3, const float* b3,
+                                   const float* fs1, const float* fs0, int slot_div, int slot_off, const float* hyper, float* masks4, int P, const uint8_t* live,
+                                   const float* iou4, int multimask, unsigned int* sentinel, void* stream) {
+    if (P <= 0) return 0;
+    if (!X || !w0 || !b0 || !ln_gamma || !ln_beta || !w3 || !b3 || !fs1 || !fs0 || !hyper || !masks4) return kfail("dec_upscale: null pointer");
+    if (slot_div <= 0 || slot_off < 0) return kfail("dec_upscale: slot_div must be positive and slot_off non-negative");
+    hipStream_t s = (hipStream_t)stream;
+    const bool f16 = saber_op_is_f16();
+    // checkpoint tensors -> host (hipMemcpyDefault: device or host pointers)
+    std::vector<float> hw0((size_t)256 * 64 * 4), hb0(64), hw3((size_t)64 * 32 * 4), hb3(32);
+    hipError_t st = hipMemcpyAsync(hw0.data(), w0, hw0.size() * 4, hipMemcpyDefault, s);
+    if (st == hipSuccess) st = hipMemcpyAsync(hb0.data(), b0, hb0.size() * 4, hipMemcpyDefault, s);
+    if (st == hipSuccess) st = hipMemcpyAsync(hw3.data(), w3, hw3.size() * 4, hipMemcpyDefault, s);
+    if (st == hipSuccess) st = hipMemcpyAsync(hb3.data(), b3, hb3.size() * 4, hipMemcpyDefault, s);
+    if (st == hipSuccess) st = hipStreamSynchronize(s);
+    if (st != hipSuccess) return kfail(hipGetErrorString(st));
+    UpscalePack up;
+    saber_pack_upscale(hw0.data(), hb0.data(), hw3.data(), hb3.data(), &up);
+    // one temporary: W1 [256][256] | W2p [128][64] (16-bit operand type) | b1 [256] | b2 [128] (fp32)
+    const size_t n1 = up.w1.size(), n2 = up.w2p.size(), w_bytes = (n1 + n2) * sizeof(bf16_t);
+    std::vector<unsigned char> host(w_bytes + (up.b1.size() + up.b2.size()) * 4);
+    bf16_t* hw = reinterpret_cast<bf16_t*>(host.data());
+    for (size_t i = 0; i < n1 + n2; ++i) {
+        const float v = i < n1 ? up.w1[i] : up.w2p[i - n1];
+        if (f16 && !(std::fabs(v) <= 65504.0f)) return kfail("dec_upscale: a weight exceeds the fp16 range (65504)");      // as saber_engine_finalize refuses it
+        hw[i] = saber_host_f2op(v, f16);
+    }
+    memcpy(host.data() + w_bytes, up.b1.data(), up.b1.size() * 4);
+    memcpy(host.data() + w_bytes + up.b1.size() * 4, up.b2.data(), up.b2.size() * 4);
+    unsigned char* dev = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&dev), host.size()) != hipSuccess) return kfail("dec_upscale: allocation of the packed weights failed");
+    int rc = 0;
+    st = hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, s);
+    if (st != hipSuccess) rc = kfail(hipGetErrorString(st));
+    if (rc == 0) {
+        const bf16_t* W1 = reinterpret_cast<const bf16_t*>(dev);
+        const float* b1 = reinterpret_cast<const float*>(dev + w_bytes);
+        rc = kcheck(launch_dec_upscale(X, W1, b1, ln_gamma, ln_beta, W1 + n1, b1 + up.b1.size(), fs1, fs0, XMap{0, slot_div, slot_off}, hyper, masks4, P, s, live, iou4,
+                                       multimask, sentinel));
+    }
+    st = hipStreamSynchronize(s);          // the launch has completed (and the upload has left `host`) before either temporary goes
+    (void)hipFree(dev);
+    if (rc == 0 && st != hipSuccess) rc = kfail(hipGetErrorString(st));
+    return rc;
+}
+extern "C" int saber_k_mask_pick(const float* masks4, const float* iou4, int P, int multimask, float* out_iou, int* out_sel, const uint8_t* live, void* stream) {
+    if (P > 0 && (!iou4 || !out_iou || (!multimask && !masks4))) return kfail("mask_pick: null pointer");
+    return kcheck(launch_mask_pick(masks4, iou4, P, multimask, out_iou, out_sel, (hipStream_t)stream, live));
+}
+extern "C" int saber_k_mask_select(const float* masks4, const float* iou4, int P, int multimask, float* out_masks, float* out_iou, void* stream) {
+    if (P > 0 && (!masks4 || !iou4 || !out_masks || !out_iou)) return kfail("mask_select: null pointer");
+    // counts_ws: the engine passes its [2 P] workspace; neither form of the kernel reads it (the dynamic form counts in its own block, the
+    // multimask form copies planes 1-3), so none is allocated here
+    return kcheck(launch_mask_select(masks4, iou4, P, multimask, out_masks, out_iou, nullptr, (hipStream_t)stream));
+}
+extern "C" int saber_k_iou_live_flags(const float* iou4, int P, float thr, uint8_t* live, unsigned long long* counters, void* stream) {
+    if (P > 0 && (!iou4 || !live)) return kfail("iou_live_flags: null pointer");
+    return kcheck(launch_iou_live_flags(iou4, P, thr, live, counters, (hipStream_t)stream));
 }
 
 int g_saber_debug_flags = 0;

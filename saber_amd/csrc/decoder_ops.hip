@@ -493,40 +493,6 @@ const char* launch_dec_attention(const float* q, const float* k, const float* v,
 }
 
 // ------------------------------------------------------------------------------------------------
-// hypernetwork product: masks[p][k][y][x] = sum_c hyper[p][k][c] * up[p][perm(y,x)][c]
-__global__ __launch_bounds__(256) void mask_dot_kernel(const bf16_t* __restrict__ up, const float* __restrict__ hyper, int P,
-                                                       float* __restrict__ masks4) {
-    __shared__ float hs[4][32];
-    const int p = blockIdx.y;
-    if (threadIdx.x < 128) hs[threadIdx.x >> 5][threadIdx.x & 31] = hyper[(int64_t)p * 128 + threadIdx.x];
-    __syncthreads();
-    const int pix = blockIdx.x * 256 + threadIdx.x;  // row-major output pixel
-    const int y = pix >> 8, x = pix & 255;
-    const int tok = perm_index256(y, x);
-    const uint4* src = reinterpret_cast<const uint4*>(up + ((int64_t)p * 65536 + tok) * 32);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint4 u = src[q];
-        const uint32_t wds[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float lo = op16_lo(wds[j]), hi = op16_hi(wds[j]);
-            const int c = q * 8 + j * 2;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) acc[kk] += hs[kk][c] * lo + hs[kk][c + 1] * hi;
-        }
-    }
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) masks4[((int64_t)p * 4 + kk) * 65536 + pix] = acc[kk];
-}
-
-const char* launch_mask_dot(const bf16_t* up, const float* hyper, int P, float* masks4, hipStream_t s) {
-    if (P <= 0) return nullptr;
-    hipLaunchKernelGGL(mask_dot_kernel, dim3(256, P), dim3(256), 0, s, up, hyper, P, masks4);
-    return nullptr;
-}
-
 // dynamic multimask: counts of mask0 > +delta, > -delta
 __global__ __launch_bounds__(256) void mask_select_kernel(const float* __restrict__ masks4, const float* __restrict__ iou4, int multimask,
                                                           float* __restrict__ out_masks, float* __restrict__ out_iou,

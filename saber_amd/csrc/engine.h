@@ -220,6 +220,17 @@ int exact_decode_core(saber_engine* e, int slot0, int per_slot, int p_base, cons
                       float mask_clamp, int mask_in_q0, float* out_obj, float* masks4, hipStream_t s, int n_pts = 1);
 int exact_chunk_prompts(const saber_engine* e);
 void exact_release(saber_engine* e);
+// The upscaling head's weights as dec_upscale_kernel reads them, packed on the host from the checkpoint layout (engine.hip; shared by
+// saber_engine_finalize and the kernel-level entry point saber_k_dec_upscale, so that the packing itself is under test).
+// ConvTranspose2d(k2,s2) as a GEMM: row n = (ky*2+kx)*Cout + co, column = ci.  w0 = output_upscaling.0.weight [256][64][2][2], w3 = .3.weight [64][32][2][2].
+struct UpscalePack {
+    std::vector<float> w1, b1;     // [256][256], [256]: ConvT 256 -> 64, the bias repeated per position
+    std::vector<float> w2, b2;     // [128][64], [128]: ConvT 64 -> 32 (the exact mode's GEMM operand)
+    std::vector<float> w2p;        // w2 with the contraction index permuted to the k-slot order phase A of dec_upscale_kernel leaves in registers:
+                                   // slot 8g+j of k-step ks <- channel 32ks + 4g + j (j<4) | 32ks + 16 + 4g + (j-4) (j>=4)
+};
+void saber_pack_upscale(const float* w0, const float* b0, const float* w3, const float* b3, UpscalePack* out);
+bf16_t saber_host_f2op(float f, bool f16);      // fp32 -> the 16-bit operand type's bits (RNE), as every weight is converted at finalize
 template <typename T> int eng_alloc(saber_engine* e, T** p, size_t count);
 int eng_alloc_bytes(saber_engine* e, void** p, size_t bytes);
 void eng_free(saber_engine* e, void* p);

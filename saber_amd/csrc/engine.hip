@@ -276,6 +276,33 @@ bf16_t saber_host_f2h(float f) {
     return (bf16_t)(sign | h);
 }
 static inline bf16_t host_f2op(float f, bool f16) { return f16 ? saber_host_f2h(f) : host_f2bf(f); }
+bf16_t saber_host_f2op(float f, bool f16) { return host_f2op(f, f16); }
+
+void saber_pack_upscale(const float* w0, const float* b0, const float* w3, const float* b3, UpscalePack* out) {
+    // ConvTranspose2d(k2,s2) as a GEMM: N index = (ky*2+kx)*Cout + co
+    auto convT = [](const float* w, const float* b, int cin, int cout, std::vector<float>* wt, std::vector<float>* bt) {
+        wt->assign((size_t)4 * cout * cin, 0.f); bt->assign((size_t)4 * cout, 0.f);
+        for (int pos = 0; pos < 4; ++pos)
+            for (int co = 0; co < cout; ++co) {
+                (*bt)[(size_t)pos * cout + co] = b[co];
+                for (int ci = 0; ci < cin; ++ci)
+                    (*wt)[((size_t)pos * cout + co) * cin + ci] = w[(((size_t)ci * cout + co) * 2 + (pos >> 1)) * 2 + (pos & 1)];
+            }
+    };
+    convT(w0, b0, 256, 64, &out->w1, &out->b1);
+    convT(w3, b3, 64, 32, &out->w2, &out->b2);
+    // dc2 weight with the contraction index permuted to the k-slot order phase A leaves in registers:
+    // slot 8g+j of k-step ks <- channel 32ks + 4g + j (j<4) | 32ks + 16 + 4g + (j-4) (j>=4)
+    out->w2p.assign((size_t)128 * 64, 0.f);
+    for (int pos = 0; pos < 4; ++pos)
+        for (int co = 0; co < 32; ++co)
+            for (int ks = 0; ks < 2; ++ks)
+                for (int g = 0; g < 4; ++g)
+                    for (int jj = 0; jj < 8; ++jj) {
+                        const int ci = jj < 4 ? 32 * ks + 4 * g + jj : 32 * ks + 16 + 4 * g + (jj - 4);
+                        out->w2p[((size_t)pos * 32 + co) * 64 + ks * 32 + g * 8 + jj] = w3[(((size_t)ci * 32 + co) * 2 + (pos >> 1)) * 2 + (pos & 1)];
+                    }
+}
 
 struct Finalizer {
     saber_engine* e;
@@ -662,38 +689,18 @@ extern "C" int saber_engine_finalize(saber_engine* e) {
         if (F.status != SABER_OK) return F.status;
         for (LinW* lw : {&e->final_attn.q, &e->final_attn.o}) TRY(pack_for_tokens(lw, lw->out));
         e->final_ln = F.ln(d + "transformer.norm_final_attn", 256);
-        // ConvTranspose2d(k2,s2) as a GEMM: N index = (ky*2+kx)*Cout + co
-        auto convT = [&](const std::string& prefix, int cin, int cout, LinW* out) {
-            const HostTensor* w = F.get(prefix + ".weight", {cin, cout, 2, 2});
-            const HostTensor* b = F.get(prefix + ".bias", {cout});
-            if (!w || !b) return;
-            std::vector<float> wt((size_t)4 * cout * cin), bt((size_t)4 * cout);
-            for (int pos = 0; pos < 4; ++pos)
-                for (int co = 0; co < cout; ++co) {
-                    bt[(size_t)pos * cout + co] = b->data[co];
-                    for (int ci = 0; ci < cin; ++ci)
-                        wt[((size_t)pos * cout + co) * cin + ci] = w->data[(((size_t)ci * cout + co) * 2 + (pos >> 1)) * 2 + (pos & 1)];
-                }
-            F.up_lin(out, wt, 4 * cout, cin); out->b = F.up_f32(bt);
-        };
-        convT(d + "output_upscaling.0", 256, 64, &e->dc1);
-        e->up_ln = F.ln(d + "output_upscaling.1", 64);
-        convT(d + "output_upscaling.3", 64, 32, &e->dc2);
-        {   // dc2 weight with the contraction index permuted to the k-slot order phase A leaves in registers:
-            // slot 8g+j of k-step ks <- channel 32ks + 4g + j (j<4) | 32ks + 16 + 4g + (j-4) (j>=4)
-            const HostTensor* w = F.get(d + "output_upscaling.3.weight", {64, 32, 2, 2});
-            if (w) {
-                std::vector<float> wp((size_t)128 * 64);
-                for (int pos = 0; pos < 4; ++pos)
-                    for (int co = 0; co < 32; ++co)
-                        for (int ks = 0; ks < 2; ++ks)
-                            for (int g = 0; g < 4; ++g)
-                                for (int jj = 0; jj < 8; ++jj) {
-                                    const int ci = jj < 4 ? 32 * ks + 4 * g + jj : 32 * ks + 16 + 4 * g + (jj - 4);
-                                    wp[((size_t)pos * 32 + co) * 64 + ks * 32 + g * 8 + jj] = w->data[(((size_t)ci * 32 + co) * 2 + (pos >> 1)) * 2 + (pos & 1)];
-                                }
-                e->dc2p = F.up_bf16(wp);
-            }
+        {   // the upscaling head: ConvTranspose2d(k2,s2) as GEMMs + the k-slot-permuted copy of the second one (saber_pack_upscale)
+            const HostTensor* w0 = F.get(d + "output_upscaling.0.weight", {256, 64, 2, 2});
+            const HostTensor* b0 = F.get(d + "output_upscaling.0.bias", {64});
+            const HostTensor* w3 = F.get(d + "output_upscaling.3.weight", {64, 32, 2, 2});
+            const HostTensor* b3 = F.get(d + "output_upscaling.3.bias", {32});
+            if (!w0 || !b0 || !w3 || !b3) return F.status;
+            UpscalePack up;
+            saber_pack_upscale(w0->data.data(), b0->data.data(), w3->data.data(), b3->data.data(), &up);
+            F.up_lin(&e->dc1, up.w1, 256, 256); e->dc1.b = F.up_f32(up.b1);
+            e->up_ln = F.ln(d + "output_upscaling.1", 64);
+            F.up_lin(&e->dc2, up.w2, 128, 64); e->dc2.b = F.up_f32(up.b2);
+            e->dc2p = F.up_bf16(up.w2p);
         }
         const int hdims[3][2] = {{256, 256}, {256, 256}, {32, 256}};
         for (int l = 0; l < 3; ++l) {

@@ -185,7 +185,7 @@ SABER_OP_INIT(decoder_fused_init_device) SABER_OP_INIT(decoder_tokens_init_devic
 SABER_OP_FWD(launch_gemm) SABER_OP_FWD(gemm_rowln_supported) SABER_OP_FWD(launch_gemm_rowln) SABER_OP_FWD(gemm_rowln_packed_elems) SABER_OP_FWD(launch_pack_w_kstep)
 SABER_OP_FWD(launch_layernorm) SABER_OP_FWD(launch_gather_rows) SABER_OP_FWD(launch_add_to_bf16) SABER_OP_FWD(launch_hiera_attention)
 SABER_OP_FWD(launch_prompt_tokens) SABER_OP_FWD(launch_prompt_tokens_multi) SABER_OP_FWD(launch_mask_embed_src) SABER_OP_FWD(launch_mask_hidden) SABER_OP_FWD(launch_embb_tiles)
-SABER_OP_FWD(launch_dec_attention) SABER_OP_FWD(launch_mask_dot) SABER_OP_FWD(launch_mask_pick) SABER_OP_FWD(launch_iou_live_flags) SABER_OP_FWD(launch_mask_select)
+SABER_OP_FWD(launch_dec_attention) SABER_OP_FWD(launch_mask_pick) SABER_OP_FWD(launch_iou_live_flags) SABER_OP_FWD(launch_mask_select)
 SABER_OP_FWD(launch_dec_fold) SABER_OP_FWD(launch_dec_t2i) SABER_OP_FWD(launch_dec_i2t) SABER_OP_FWD(launch_dec_i2t_t2i) SABER_OP_FWD(launch_dec_upscale) SABER_OP_FWD(launch_dec_tokens)
 SABER_OP_FWD(launch_prompt_tokens16) SABER_OP_FWD(launch_dec_tokens16) SABER_OP_FWD(launch_dec_i2t16)
 SABER_OP_FWD(launch_mask_post) SABER_OP_FWD(launch_gather_masks) SABER_OP_FWD(launch_label_plane) SABER_OP_FWD(launch_pair_intersections) SABER_OP_FWD(launch_unpermute_nchw)

@@ -41,8 +41,6 @@ const char* launch_embb_tiles(const float* emb, const float* b3, float* out, hip
 // Output is bf16 (it always feeds the out_proj GEMM).
 const char* launch_dec_attention(const float* q, const float* k, const float* v, bf16_t* out, int B, int nq, int nk, int heads,
                                  int hd, int64_t q_bs, int64_t k_bs, int64_t v_bs, int64_t o_bs, hipStream_t s);
-// masks[p][k][y][x] = sum_c hyper[p][k][c] * up[p][perm(y,x)][c]  (up: bf16 [P][65536][32], engine token order)
-const char* launch_mask_dot(const bf16_t* up, const float* hyper, int P, float* masks4, hipStream_t s);
 // multimask: out[p][0..2] = masks4[p][1..3], iou_out = iou4[:,1:]; else dynamic single-mask selection (delta 0.05 / thr 0.98)
 const char* launch_mask_pick(const float* masks4, const float* iou4, int P, int multimask, float* out_iou, int* out_sel, hipStream_t s, const uint8_t* live = nullptr);
 // live[p] = iou4[p][0] > thr || max(iou4[p][1..3]) > thr: whether a single-mask (dynamic multimask) candidate can pass a `predicted IoU > thr` filter at all
@@ -65,7 +63,8 @@ const char* launch_dec_i2t_t2i(const bf16_t* X, XMap xm, const bf16_t* peq, cons
 const char* launch_dec_upscale(const bf16_t* X, const bf16_t* W1, const float* b1, const float* ln_g, const float* ln_b, const bf16_t* W2p,
                                const float* b2, const float* fs1, const float* fs0, XMap slot_map, const float* hyper, float* masks4, int P,
                                hipStream_t s, const uint8_t* live = nullptr, const float* iou4 = nullptr, int multimask = 0, unsigned int* sentinel = nullptr);
-// sentinel (optional): += number of lanes that stored a NaN / inf logit
+// sentinel (optional): += number of lanes that stored a NaN / inf logit (a lane of a workgroup counts once per launch, however many pixels and prompts it
+// stored: non-zero = something overflowed, not a pixel count)
 // live: optional per-prompt flags, prompts with 0 are skipped; iou4 ([P][4], optional): only the planes a multimask / single-mask selection can return are computed
 const char* decoder_fused_init_device();
 const char* launch_dec_tokens(const TokSeg& s, hipStream_t st);
