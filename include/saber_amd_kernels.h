@@ -194,6 +194,39 @@ void saber_k_set_stamp_buffer(void* dev);
 
 int saber_k_perm_index(int y, int x, int stage);
 
+/* ---- the exact-precision (fp32) kernels of saber_engine_set_precision(e, SABER_PRECISION_EXACT) (csrc/exact.hip), through the launchers the
+ * engine calls: every operand, product, sum and statistic in fp32.  Device pointers, row-major with explicit leading dimensions (in floats). */
+/* C[b][m][n] = epi(sum_k A'[b][m][k] W[b][n][k] + bias[b][n]) for b < batch (A + b sA, W + b sW, bias + b sBias, C + b sC), with
+ * A'[m][k] = A[m][k] + A2[m % a2_mod][k] summed in fp32 when A2 is given.  epi: act (0 none, 1 GELU(erf), 2 ReLU, 3 sigmoid), then + res;
+ * act_last: + res, then act.  Residual row of output row m: res_rows_per > 0: ((m / res_rows_per + res_off) / res_div) * res_stride +
+ * (m % res_rows_per) * ldres; else ((m >> res_shift) % res_mod, or without the modulo when res_mod = 0) * ldres.  pool4: output row q = max over
+ * rows 4q .. 4q+3, + bias (M % 4 == 0; refused with act, act_last, res or A2).  A2 and the per-slot residual need 16-byte aligned rows. */
+int saber_k_xg_gemm(const float* A, int64_t lda, int64_t sA, const float* A2, int64_t lda2, int64_t a2_mod, const float* W, int64_t ldw, int64_t sW,
+                    const float* bias, int64_t sBias, const float* res, int64_t ldres, int res_shift, int64_t res_mod, int64_t res_rows_per,
+                    int64_t res_stride, int res_div, int res_off, float* C, int64_t ldc, int64_t sC, int M, int N, int K, int act, int act_last,
+                    int pool4, int batch, void* stream);
+/* out = act(LayerNorm(x) * gamma + beta) over rows of C contiguous floats (biased two-pass variance); row_valid (optional): row r is written as
+ * zeros where row_valid[r % valid_mod] == 0 */
+int saber_k_xg_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* out, int64_t rows, int C, int act,
+                         const uint8_t* row_valid, int valid_mod, void* stream);
+/* o[b][i][h*hd + d] = sum_j softmax_j(scale q_i . k_j) v_j[h*hd + d] per batch entry b and head h (row pointers base + b *_bs + i * ld);
+ * hd 16, 32, 56, 72 or 96.  qpool: query i is the element-wise maximum of q rows 4i .. 4i+3; kmask (optional, nk bytes shared by every batch
+ * entry): 0 = the key takes no part */
+int saber_k_xg_attention(int hd, const float* q, int64_t q_bs, int ldq, const float* k, int64_t k_bs, int ldk, const float* v, int64_t v_bs, int ldv,
+                         float* o, int64_t o_bs, int ldo, int nq, int nk, int batch, int heads, int qpool, const uint8_t* kmask, float scale, void* stream);
+/* out[r][c] = x[r][c] + y[(ymod ? r % ymod : r)][c] */
+int saber_k_xg_add(const float* x, const float* y, int64_t ymod, float* out, int64_t rows, int C, void* stream);
+/* out[p][j] = act((in ? in[p][j] : 0) + tab[((p + off) / div) * stride + j] + (vec ? vec[j % C] : 0)), j < rows_per * C, p < P */
+int saber_k_xg_add_slot(const float* in, const float* tab, int64_t stride, int div, int off, const float* vec, float* out, int64_t rows_per, int C,
+                        int P, int act, void* stream);
+/* the mask prompt's first two stages: out[p][tok][16] = GELU(LN2d(conv k2s2 4->16 (GELU(LN2d(conv k2s2 1->4 (plane))))))), tok = saber_k_perm_index
+ * order of the 64 x 64 grid, eps 1e-6; plane = mask_in + q * 65536 (256 x 256), q = p, or with raw4_q0 >= 0: q = i + i / 3 + 1 for i = raw4_q0 + p;
+ * clamp_abs > 0 clamps the mask to +-clamp_abs first.  w1 [4][1][2][2], b1, g1, be1 [4]; w2 [16][4][2][2], b2, g2, be2 [16] */
+int saber_k_xg_mask_hidden(const float* mask_in, int P, const float* w1, const float* b1, const float* g1, const float* be1, const float* w2,
+                           const float* b2, const float* g2, const float* be2, float clamp_abs, int raw4_q0, float* out, void* stream);
+/* masks4[p][k][y][x] = sum_c hyper[p][k][c] up[p][saber_k_perm_index(y, x, 0)][c]; up [P][65536][32], hyper [P][4][32], masks4 [P][4][256][256] */
+int saber_k_xg_mask_dot(const float* up, const float* hyper, int P, float* masks4, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

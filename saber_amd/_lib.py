@@ -142,6 +142,14 @@ SIGNATURES = {
     "saber_k_add_to_bf16": (_i, [_vp, _vp, _i, _vp, _vp, C.c_int64, _i, _vp]),
     "saber_k_bf16_to_f32": (_i, [_vp, C.c_int64, _vp, _vp]),
     "saber_k_gemm_batched": (_i, [_vp, _i, C.c_int64, _vp, _i, C.c_int64, _vp, _vp, _i, C.c_int64, _vp, _i, C.c_int64, _i, _i, _i, _i, _vp]),
+    "saber_k_xg_gemm": (_i, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _i,
+                             C.c_int64, C.c_int64, C.c_int64, _i, _i, _vp, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "saber_k_xg_layernorm": (_i, [_vp, _vp, _vp, _f, _vp, C.c_int64, _i, _i, _vp, _i, _vp]),
+    "saber_k_xg_attention": (_i, [_i, _vp, C.c_int64, _i, _vp, C.c_int64, _i, _vp, C.c_int64, _i, _vp, C.c_int64, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
+    "saber_k_xg_add": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, _i, _vp]),
+    "saber_k_xg_add_slot": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, _vp, C.c_int64, _i, _i, _i, _vp]),
+    "saber_k_xg_mask_hidden": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp]),
+    "saber_k_xg_mask_dot": (_i, [_vp, _vp, _i, _vp, _vp]),
     "saber_k_set_debug": (None, [_i]),
     "saber_k_set_stamp_buffer": (None, [_vp]),
 }

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "engine.h"
+#include "exact.h"
 
 #include <atomic>
 
@@ -315,3 +316,53 @@ extern "C" int saber_k_gemm_batched(const uint16_t* A, int lda, int64_t strideA,
     return kcheck(launch_gemm(p, (hipStream_t)stream));
 }
 extern "C" int saber_k_bf16_to_f32(const uint16_t* x, int64_t n, float* out, void* stream) { return kcheck(launch_bf16_to_f32(x, n, out, (hipStream_t)stream)); }
+
+// ------------------------------------------------------------------------------------------------ exact-precision (fp32) kernels (exact.hip)
+// The launchers the engine's exact mode calls, as they stand; the checks here only keep divisors and the batch count positive.
+extern "C" int saber_k_xg_gemm(const float* A, int64_t lda, int64_t sA, const float* A2, int64_t lda2, int64_t a2_mod, const float* W, int64_t ldw, int64_t sW,
+                               const float* bias, int64_t sBias, const float* res, int64_t ldres, int res_shift, int64_t res_mod, int64_t res_rows_per,
+                               int64_t res_stride, int res_div, int res_off, float* C, int64_t ldc, int64_t sC, int M, int N, int K, int act, int act_last,
+                               int pool4, int batch, void* stream) {
+    if (batch < 1) return kfail("xg_gemm: batch must be positive");
+    if (A2 && a2_mod < 1) return kfail("xg_gemm: a2_mod must be positive");
+    if (res && res_rows_per > 0 && (res_div < 1 || res_off < 0)) return kfail("xg_gemm: res_div must be positive and res_off non-negative");
+    if (res && (res_mod < 0 || res_shift < 0 || res_shift > 31)) return kfail("xg_gemm: bad residual mapping");
+    XGemm p;
+    p.A = A; p.lda = lda; p.sA = sA; p.A2 = A2; p.lda2 = lda2; p.a2_mod = a2_mod; p.W = W; p.ldw = ldw; p.sW = sW; p.bias = bias; p.sBias = sBias;
+    p.res = res; p.ldres = ldres; p.res_shift = res_shift; p.res_mod = res_mod; p.res_rows_per = res_rows_per; p.res_stride = res_stride; p.res_div = res_div;
+    p.res_off = res_off; p.C = C; p.ldc = ldc; p.sC = sC; p.M = M; p.N = N; p.K = K; p.act = act; p.act_last = act_last; p.pool4 = pool4; p.batch = batch;
+    return kcheck(xg_gemm(p, (hipStream_t)stream));
+}
+extern "C" int saber_k_xg_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* out, int64_t rows, int C, int act,
+                                    const uint8_t* row_valid, int valid_mod, void* stream) {
+    if (C < 1) return kfail("xg_layernorm: C must be positive");
+    if (row_valid && valid_mod < 1) return kfail("xg_layernorm: valid_mod must be positive");
+    return kcheck(xg_layernorm(x, LnW{gamma, beta}, eps, out, rows, C, act, (hipStream_t)stream, row_valid, valid_mod));
+}
+extern "C" int saber_k_xg_attention(int hd, const float* q, int64_t q_bs, int ldq, const float* k, int64_t k_bs, int ldk, const float* v, int64_t v_bs, int ldv,
+                                    float* o, int64_t o_bs, int ldo, int nq, int nk, int batch, int heads, int qpool, const uint8_t* kmask, float scale,
+                                    void* stream) {
+    if (nk < 1 || heads < 1) return kfail("xg_attention: nk and heads must be positive");
+    return kcheck(xg_attn(hd, q, q_bs, ldq, k, k_bs, ldk, v, v_bs, ldv, o, o_bs, ldo, nq, nk, batch, heads, qpool, kmask, scale, (hipStream_t)stream));
+}
+extern "C" int saber_k_xg_add(const float* x, const float* y, int64_t ymod, float* out, int64_t rows, int C, void* stream) {
+    if (C < 1 || ymod < 0) return kfail("xg_add: C must be positive and ymod non-negative");
+    xg_add(x, y, ymod, out, rows, C, (hipStream_t)stream);
+    return kcheck(nullptr);
+}
+extern "C" int saber_k_xg_add_slot(const float* in, const float* tab, int64_t stride, int div, int off, const float* vec, float* out, int64_t rows_per, int C,
+                                   int P, int act, void* stream) {
+    if (C < 1 || div < 1 || off < 0) return kfail("xg_add_slot: C and div must be positive and off non-negative");
+    xg_add_slot(in, tab, XMap{stride, div, off}, vec, out, rows_per, C, P, act, (hipStream_t)stream);
+    return kcheck(nullptr);
+}
+extern "C" int saber_k_xg_mask_hidden(const float* mask_in, int P, const float* w1, const float* b1, const float* g1, const float* be1, const float* w2,
+                                      const float* b2, const float* g2, const float* be2, float clamp_abs, int raw4_q0, float* out, void* stream) {
+    const MaskEmbedWeights w{w1, b1, g1, be1, w2, b2, g2, be2, nullptr, nullptr};
+    xg_mask_hidden(mask_in, P, w, clamp_abs, raw4_q0, out, (hipStream_t)stream);
+    return kcheck(nullptr);
+}
+extern "C" int saber_k_xg_mask_dot(const float* up, const float* hyper, int P, float* masks4, void* stream) {
+    xg_mask_dot(up, hyper, P, masks4, (hipStream_t)stream);
+    return kcheck(nullptr);
+}

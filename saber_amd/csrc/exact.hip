@@ -10,7 +10,7 @@
 //     attention, out projection, residual, LayerNorm; two ConvTranspose2d as GEMMs, LayerNorm2d, GELU, hypernetwork product), so it
 //     also checks the production kernels' folded t2i / i2t algebra and their fused upscaling against an independent formulation.
 // A verification mode: a default-grid AMG slice takes 1.2 s (round 3: 3.7 s) against 0.14 s of the production arithmetic.
-#include "engine.h"
+#include "exact.h"
 
 #include <algorithm>
 #include <cmath>
@@ -21,22 +21,8 @@
 #define TRY(x) do { int _r = (x); if (_r != SABER_OK) return _r; } while (0)
 
 // ------------------------------------------------------------------------------------------------ fp32 GEMM
-// C[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]) (+ res) ; 128 x 64 tile per 256-thread workgroup, 16-deep K steps through LDS,
+// C[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]) (+ res) (XGemm: exact.h); 128 x 64 tile per 256-thread workgroup, 16-deep K steps through LDS,
 // wave w owns rows 32w..32w+31 of the tile as 2 x 4 MFMA tiles of 16 x 16.
-struct XGemm {
-    const float* A = nullptr; int64_t lda = 0; int64_t sA = 0;
-    const float* W = nullptr; int64_t ldw = 0; int64_t sW = 0;
-    const float* bias = nullptr; int64_t sBias = 0;
-    const float* res = nullptr; int64_t ldres = 0; int res_shift = 0; int64_t res_mod = 0;
-    // res_rows_per > 0: per-prompt rows against per-slot tables - the residual of row r is res[((r / res_rows_per + res_off) / res_div) * res_stride +
-    // (r % res_rows_per) * ldres + n] (the xg_add_slot mapping folded into the epilogue)
-    int64_t res_rows_per = 0, res_stride = 0; int res_div = 1, res_off = 0;
-    // A2: the operand is A[m][k] + A2[(m % a2_mod)][k], summed in fp32 before the product exactly as a stored sum would be (keys + dense_pe)
-    const float* A2 = nullptr; int64_t lda2 = 0; int64_t a2_mod = 1;
-    int64_t row0 = 0;      // first row of this launch within the whole GEMM (row slabs): the A2 and slot-residual mappings count from there
-    float* C = nullptr; int64_t ldc = 0; int64_t sC = 0;
-    int M = 0, N = 0, K = 0, act = ACT_NONE, act_last = 0, pool4 = 0, batch = 1;
-};
 
 __device__ __attribute__((noinline)) float x_gelu(float x) {   // noinline: 64 epilogue values x libm erff would be 50 k instructions per GEMM kernel
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
@@ -299,10 +285,13 @@ __global__ __launch_bounds__(256, 3) void xg_gemm2_kernel(XGemm p) {
         }
     }
 }
-static const char* xg_gemm(const XGemm& p, hipStream_t s) {
+const char* xg_gemm(const XGemm& p, hipStream_t s) {
     if (p.M <= 0 || p.N <= 0) return nullptr;
     if (!p.A || !p.W || !p.C || p.K <= 0) return "exact gemm: bad argument";
     if (p.pool4 && (p.M % 4)) return "exact gemm: pool4 needs M % 4 == 0";
+    // both kernels leave the pool4 epilogue before the residual and act_last, and apply the activation after the maximum (launch_gemm, gemm.hip:
+    // activation, pool, residual): combinations the engine never asks for are refused rather than computed differently
+    if (p.pool4 && (p.res || p.act_last || p.A2 || p.act != ACT_NONE)) return "exact gemm: pool4 takes no residual, act_last, A2 or activation";
     const bool vec = ((p.lda | p.ldw | p.sA | p.sW | (int64_t)p.K) & 3) == 0 && ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.W)) & 15) == 0 &&
                      (!p.A2 || (((p.lda2 & 3) == 0) && (reinterpret_cast<uintptr_t>(p.A2) & 15) == 0));
     if (!vec && (p.A2 || p.res_rows_per > 0)) return "exact gemm: the fused operand sum / slot residual need 16-byte rows";
@@ -325,8 +314,10 @@ static const char* xg_gemm(const XGemm& p, hipStream_t s) {
         return nullptr;
     }
     if (gy > 65535 * 32) return "exact gemm: M too large";
-    // gridDim.y is limited to 65535: large M is split into row slabs
+    // gridDim.y is limited to 65535: large M is split into row slabs (a residual row map by shift / modulo counts from the slab's first row:
+    // refused beyond one slab, before anything is launched)
     const int64_t slab = 65535;
+    if (p.res && (p.res_mod > 0 || p.res_shift) && gy > slab) return "exact gemm: residual mapping with M beyond one slab";
     for (int64_t y0 = 0; y0 < gy; y0 += slab) {
         XGemm q = p;
         const int64_t rows0 = y0 * XG_BM;
@@ -335,10 +326,7 @@ static const char* xg_gemm(const XGemm& p, hipStream_t s) {
         q.C = p.C + (p.pool4 ? rows0 / 4 : rows0) * p.ldc;
         q.M = (int)std::min<int64_t>((int64_t)p.M - rows0, ny * XG_BM);
         q.row0 = rows0;
-        if (p.res) {
-            if (p.res_mod > 0 || p.res_shift) { if (y0 > 0) return "exact gemm: residual mapping with M beyond one slab"; }
-            else if (p.res_rows_per <= 0) q.res = p.res + rows0 * p.ldres;
-        }
+        if (p.res && !(p.res_mod > 0 || p.res_shift) && p.res_rows_per <= 0) q.res = p.res + rows0 * p.ldres;
         hipLaunchKernelGGL(xg_gemm_kernel, dim3((p.N + XG_BN - 1) / XG_BN, (unsigned)ny, p.batch), dim3(256), 0, s, q);
     }
     return nullptr;
@@ -419,8 +407,8 @@ __global__ __launch_bounds__(256) void xg_layernorm4_kernel(const float* __restr
         o[c] = r;
     }
 }
-static const char* xg_layernorm(const float* x, const LnW& w, float eps, float* out, int64_t rows, int C, int act, hipStream_t s,
-                                const uint8_t* row_valid = nullptr, int valid_mod = 0) {
+const char* xg_layernorm(const float* x, const LnW& w, float eps, float* out, int64_t rows, int C, int act, hipStream_t s, const uint8_t* row_valid,
+                         int valid_mod) {
     if (rows <= 0) return nullptr;
     const bool al = (C & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(w.g) | reinterpret_cast<uintptr_t>(w.b)) & 15) == 0;
     if (al && C == 64 && !row_valid)
@@ -445,7 +433,7 @@ __global__ __launch_bounds__(256) void xg_add_kernel(const float* __restrict__ x
         out[i] = x[i] + y[(ymod ? r % ymod : r) * C + c];
     }
 }
-static void xg_add(const float* x, const float* y, int64_t ymod, float* out, int64_t rows, int C, hipStream_t s) {
+void xg_add(const float* x, const float* y, int64_t ymod, float* out, int64_t rows, int C, hipStream_t s) {
     if (rows <= 0) return;
     const int64_t total = rows * C;
     hipLaunchKernelGGL(xg_add_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65536 * 8)), dim3(256), 0, s, x, y, ymod, out, rows, C);
@@ -478,7 +466,7 @@ __global__ __launch_bounds__(256) void xg_add_slot4_kernel(const f32x4* __restri
         out[i] = v;
     }
 }
-static void xg_add_slot(const float* in, const float* tab, XMap m, const float* vec, float* out, int64_t rows_per, int C, int P, int act, hipStream_t s) {
+void xg_add_slot(const float* in, const float* tab, XMap m, const float* vec, float* out, int64_t rows_per, int C, int P, int act, hipStream_t s) {
     if (P <= 0) return;
     const int64_t total = rows_per * C * P;
     if ((C & 3) == 0 && (m.stride & 3) == 0 &&
@@ -928,8 +916,8 @@ __global__ __launch_bounds__(256) void xg_attn_fewk_kernel(const float* __restri
 #pragma unroll
     for (int c = 0; c < 4; ++c) op[c] = (f32x4){acc[4 * c] * inv, acc[4 * c + 1] * inv, acc[4 * c + 2] * inv, acc[4 * c + 3] * inv};
 }
-static const char* xg_attn(int hd, const float* q, int64_t q_bs, int ldq, const float* k, int64_t k_bs, int ldk, const float* v, int64_t v_bs, int ldv,
-                           float* o, int64_t o_bs, int ldo, int nq, int nk, int batch, int heads, int qpool, const uint8_t* kmask, float scale, hipStream_t s) {
+const char* xg_attn(int hd, const float* q, int64_t q_bs, int ldq, const float* k, int64_t k_bs, int ldk, const float* v, int64_t v_bs, int ldv,
+                    float* o, int64_t o_bs, int ldo, int nq, int nk, int batch, int heads, int qpool, const uint8_t* kmask, float scale, hipStream_t s) {
     if (batch <= 0 || nq <= 0) return nullptr;
     if (hd == 16 && nq <= 16 && nk >= 1024 && !qpool && !kmask && batch <= 65535 && ((ldk | ldv) & 3) == 0 && (((k_bs | v_bs) & 3) == 0) &&
         ((reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) & 15) == 0) {
@@ -1067,6 +1055,14 @@ __global__ __launch_bounds__(256) void xg_mask_dot_kernel(const float* __restric
         for (int c = 0; c < 32; ++c) a = fmaf(hp[kq * 32 + c], uv[c], a);
         masks4[((int64_t)p * 4 + kq) * 65536 + pix] = a;
     }
+}
+void xg_mask_hidden(const float* mask_in, int P, const MaskEmbedWeights& w, float clamp_abs, int raw4_q0, float* h2out, hipStream_t s) {
+    if (P <= 0) return;
+    hipLaunchKernelGGL(xg_mask_hidden_kernel, dim3((unsigned)(((int64_t)P * 4096 + 255) / 256)), dim3(256), 0, s, mask_in, P, w, clamp_abs, raw4_q0, h2out);
+}
+void xg_mask_dot(const float* up, const float* hyper, int P, float* masks4, hipStream_t s) {
+    if (P <= 0) return;
+    hipLaunchKernelGGL(xg_mask_dot_kernel, dim3((unsigned)(((int64_t)P * 65536 + 255) / 256)), dim3(256), 0, s, up, hyper, P, masks4);
 }
 
 // ------------------------------------------------------------------------------------------------ workspaces
@@ -1259,7 +1255,7 @@ int exact_decode_core(saber_engine* e, int slot0, int per_slot, int p_base, cons
     if (!mask_in) {
         xg_add_slot(nullptr, emb0, slots, e->no_mask_embed, w->keys, 4096, 256, P, ACT_NONE, s);
     } else {
-        hipLaunchKernelGGL(xg_mask_hidden_kernel, dim3((unsigned)(((int64_t)P * 4096 + 255) / 256)), dim3(256), 0, s, mask_in, P, e->mw, mask_clamp, mask_in_q0, w->h2);
+        xg_mask_hidden(mask_in, P, e->mw, mask_clamp, mask_in_q0, w->h2, s);
         XGemm g;
         g.A = w->h2; g.lda = 16; g.W = e->mw.w3; g.ldw = 16; g.bias = e->mw.b3; g.M = P * 4096; g.N = 256; g.K = 16; g.C = w->keys; g.ldc = 256;
         XK(xg_gemm(g, s));
@@ -1362,7 +1358,7 @@ int exact_decode_core(saber_engine* e, int slot0, int per_slot, int p_base, cons
         g.res = e->fs0 + (size_t)slot0 * 65536 * 32; g.ldres = 128; g.res_rows_per = 16384; g.res_stride = (int64_t)65536 * 32; g.res_div = per_slot; g.res_off = p_base;
         XK(xg_gemm(g, s));
     }
-    hipLaunchKernelGGL(xg_mask_dot_kernel, dim3((unsigned)(((int64_t)P * 65536 + 255) / 256)), dim3(256), 0, s, w->up2, e->hyper_out, P, masks4);
+    xg_mask_dot(w->up2, e->hyper_out, P, masks4, s);
     ENG_HIP(e, hipGetLastError());
     return SABER_OK;
 }
