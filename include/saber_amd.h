@@ -272,6 +272,47 @@ int saber_smooth_labels(saber_engine* e, const void* labels_dev, int elem_bytes,
  * out_dev (Z,H,W) float32. */
 int saber_gaussian_smoothing_3d(saber_engine* e, const uint8_t* mask_dev, int Z, int H, int W, double sigma, float* out_dev, void* stream);
 
+/* ---- organelle / membrane refinement (saber/analysis/refine_membranes.py), csrc/morph3d.hip.  Only a created handle is needed. ----
+ * Binary dilation (op 0), erosion (op 1) or opening (op 2: erosion, then dilation) of a 0/1 volume by the ball of `radius` 1..16 with
+ * a zero border: what _torch_dilation_3d / _torch_erosion_3d / _morphological_opening_gpu (refine_membranes.py:274-333) compute with a
+ * dense conv3d of the _create_ball_kernel structuring element (:100-117, dist^2 <= radius^2), and what the scipy.ndimage.binary_opening
+ * route (:309-319) computes on the CPU.  mask_dev, out_dev: (Z,H,W) uint8 on the engine's device, any non-zero voxel is set, the result
+ * is 0/1.  Runs on bit-packed rows; synchronises the stream. */
+int saber_morph_ball_3d(saber_engine* e, const uint8_t* mask_dev, int Z, int H, int W, int radius, int op, uint8_t* out_dev, void* stream);
+
+/* 6-connected components (scipy.ndimage.label's default structure) of the non-zero voxels of a (Z,H,W) uint8 volume.  mode 0: components
+ * with fewer than min_size voxels are zeroed (_remove_small_objects, refine_membranes.py:136-159; _remove_small_membrane_components,
+ * :201-224); mode 1: only the largest component stays, the first in raster order on ties (_get_largest_component, :226-249: argmax over
+ * scipy's label order).  out_dev keeps the input's values on the surviving voxels and may be the input itself.  *out_n_components =
+ * components kept (mode 0) or found (mode 1).  Synchronises the stream. */
+int saber_components6_3d(saber_engine* e, const uint8_t* mask_dev, int Z, int H, int W, int mode, int min_size, uint8_t* out_dev,
+                         int* out_n_components, void* stream);
+
+/* FilteringConfig (refine_membranes.py:54-63) as the device pipeline needs it.  ball_size is a RADIUS (1..16).  min_roi_size =
+ * float32(min_roi_relative_size * shape), computed by the caller with the arithmetic of _get_organelle_roi (:261-266): the size test
+ * `extent < min_roi_size` is a float32 comparison and is not re-derived here. */
+typedef struct saber_refine_params {
+    int ball_size, min_membrane_area, edge_trim_z, edge_trim_xy, keep_surface_membranes;
+    float min_roi_size[3];
+} saber_refine_params;
+
+/* OrganelleMembraneFilter.run (refine_membranes.py:445-547) with _process_organelle_batch (:335-443) on the device.  org_dev: (Z,H,W)
+ * organelle labels of elem_bytes 1, 2 or 4 (unsigned), values <= 2^22; mem_dev: (Z,H,W) uint8 membrane segmentation (non-zero = membrane).
+ * Writes the two FLATTENED label maps, convert_to_3d_labels (:549-573) of the reference's 4-D stacks: organelle v comes out as v + 1 in
+ * both maps (the reference relabels to (v + 1) * 2, :494-495, and halves at the end, :539-540), later labels overwrite earlier ones.
+ * The per-pair results (label, box, packed organelle and membrane bits) stay on the handle until the next call or destroy, for
+ * saber_refine_membranes_instances.  *out_n_labels_in = labels found on the planes that hold membrane (:479-480); *out_n_pairs = pairs
+ * that survived (planes of the reference's stacks).  SABER_ERR_INVALID when a label exceeds 2^22 or (largest label + 1) * 2 does not fit
+ * the element type (the reference wraps silently there).  Three stream synchronisations per call, whatever the number of labels. */
+int saber_refine_membranes(saber_engine* e, const void* org_dev, int elem_bytes, const uint8_t* mem_dev, int Z, int H, int W,
+                           const saber_refine_params* params, void* org_labels_out_dev, void* mem_labels_out_dev, int* out_n_labels_in,
+                           int* out_n_pairs, void* stream);
+
+/* Pairs [first, first + count) of the last saber_refine_membranes call as dense planes: the reference's 4-D stacks (:534-540), `count`
+ * planes at a time.  org_stack_dev, mem_stack_dev: (count,Z,H,W) of elem_bytes.  SABER_ERR_INVALID for a range outside [0, n_pairs). */
+int saber_refine_membranes_instances(saber_engine* e, int first, int count, int elem_bytes, void* org_stack_dev, void* mem_stack_dev,
+                                     void* stream);
+
 /* ---- domain-expert classifier filter on the engine's image embeddings ----
  * Replaces saber.classifier.models.predictor.Predictor (saber/classifier/models/predictor.py:9-60 construction, :117-175 predict) with the
  * SAM2Classifier model (saber/classifier/models/SAM2.py:21-197) behind it; hook: saber2D._apply_classifier -> filters.apply_classifier

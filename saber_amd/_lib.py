@@ -46,6 +46,11 @@ class MaskMeta(C.Structure):
                 ("stability_score", C.c_float), ("point_xy", C.c_float * 2), ("crop_box_xywh", C.c_float * 4)]
 
 
+class RefineParams(C.Structure):
+    _fields_ = [("ball_size", C.c_int), ("min_membrane_area", C.c_int), ("edge_trim_z", C.c_int), ("edge_trim_xy", C.c_int),
+                ("keep_surface_membranes", C.c_int), ("min_roi_size", C.c_float * 3)]
+
+
 class ProfileClass(C.Structure):
     _fields_ = [("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -88,6 +93,10 @@ SIGNATURES = {
     "saber_separate_masks": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
     "saber_smooth_labels": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, C.POINTER(_i), _vp]),
     "saber_gaussian_smoothing_3d": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp]),
+    "saber_morph_ball_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "saber_components6_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
+    "saber_refine_membranes": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(RefineParams), _vp, _vp, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "saber_refine_membranes_instances": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "saber_classifier_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "saber_classifier_destroy": (None, [_vp]),
     "saber_classifier_set_weight": (_i, [_vp, C.c_char_p, _vp, _i64p, _i]),

@@ -37,6 +37,7 @@ struct saber_engine {
     bool op_f16 = false;            // 16-bit operand type of this handle's weights / workspaces (fixed at finalize): false = bf16, true = IEEE fp16
     bool keep_f32 = false;          // fp32 weight copies were requested before finalize (exact mode available)
     void* exact_ws = nullptr;       // exact.hip's workspaces (allocated on first use)
+    void* refine_state = nullptr;   // morph3d.hip: ball tables and the pairs of the last saber_refine_membranes call (allocated on first use)
 
     // model description (tiny / small / base+ / large)
     int embed_dim = 0;
@@ -167,6 +168,7 @@ void prof_end(saber_engine* e, hipStream_t s);
     } while (0)
 
 int eng_fail(saber_engine* e, int code, const std::string& msg);
+void refine_release(saber_engine* e);       // morph3d.hip: frees refine_state
 // h[0..2]: the sentinel counters as read from the device; SABER_OK or SABER_ERR_RANGE with a message that names the stage
 int eng_check_finite_counts(saber_engine* e, const unsigned int* h);
 // Binds the calling thread to the engine's device for the duration of one C-ABI call and restores the caller's current device on

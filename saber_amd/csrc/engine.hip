@@ -227,6 +227,7 @@ extern "C" void saber_engine_destroy(saber_engine* e) {
     (void)hipDeviceSynchronize();
     for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
     exact_release(e);
+    refine_release(e);
     if (e->crops_pin) (void)hipHostFree(e->crops_pin);
     for (hipEvent_t ev : e->crops_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->enc_ev) if (ev) (void)hipEventDestroy(ev);

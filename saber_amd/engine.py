@@ -270,6 +270,49 @@ class Engine:
         self._check(self.lib.saber_gaussian_smoothing_3d(self.h, _ptr(mask), Z, H, W, float(sigma), _ptr(out), _stream()))
         return out
 
+    # ------------------------------------------------------------------ membrane refinement (csrc/morph3d.hip)
+    def morph_ball_3d(self, mask: torch.Tensor, radius: int, op: int) -> torch.Tensor:
+        """Binary dilation (op 0), erosion (1) or opening (2) by the ball of `radius` 1..16, zero border.  mask: (Z,H,W) bool / uint8
+        device tensor -> uint8 0/1."""
+        assert mask.is_cuda and mask.dim() == 3 and mask.is_contiguous() and mask.dtype in (torch.bool, torch.uint8)
+        Z, H, W = mask.shape
+        out = torch.empty((Z, H, W), dtype=torch.uint8, device=mask.device)
+        self._check(self.lib.saber_morph_ball_3d(self.h, _ptr(mask), Z, H, W, int(radius), int(op), _ptr(out), _stream()))
+        return out
+
+    def components6_3d(self, mask: torch.Tensor, mode: int, min_size: int = 0):
+        """6-connected components of a (Z,H,W) bool / uint8 device tensor.  mode 0: zero the components below min_size; mode 1: keep
+        the largest (first in raster order on ties).  Returns (uint8 tensor, components kept (mode 0) / found (mode 1))."""
+        assert mask.is_cuda and mask.dim() == 3 and mask.is_contiguous() and mask.dtype in (torch.bool, torch.uint8)
+        Z, H, W = mask.shape
+        out = torch.empty((Z, H, W), dtype=torch.uint8, device=mask.device)
+        n = C.c_int(0)
+        self._check(self.lib.saber_components6_3d(self.h, _ptr(mask), Z, H, W, int(mode), int(min_size), _ptr(out), C.byref(n), _stream()))
+        return out, n.value
+
+    def refine_membranes(self, org: torch.Tensor, mem: torch.Tensor, params: "_lib.RefineParams"):
+        """OrganelleMembraneFilter.run on the device.  org: (Z,H,W) uint8 / (u)int16 / (u)int32 labels, mem: (Z,H,W) bool / uint8.
+        Returns (organelle label map, membrane label map, surviving pairs); the maps have org's dtype, organelle v comes out as v + 1."""
+        assert org.is_cuda and org.dim() == 3 and org.is_contiguous() and mem.is_cuda and mem.is_contiguous() and mem.shape == org.shape
+        if org.dtype not in (torch.uint8, torch.int16, torch.uint16, torch.int32, torch.uint32):
+            raise ValueError(f"refine_membranes: unsupported label dtype {org.dtype}")
+        if mem.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"refine_membranes: the membrane volume must be bool or uint8, got {mem.dtype}")
+        Z, H, W = org.shape
+        org_out, mem_out = torch.empty_like(org), torch.empty_like(org)
+        n_in, n_pairs = C.c_int(0), C.c_int(0)
+        self._check(self.lib.saber_refine_membranes(self.h, _ptr(org), org.element_size(), _ptr(mem), Z, H, W, C.byref(params), _ptr(org_out),
+                                                    _ptr(mem_out), C.byref(n_in), C.byref(n_pairs), _stream()))
+        self.refine_labels_in = n_in.value
+        return org_out, mem_out, n_pairs.value
+
+    def refine_membranes_instances(self, first: int, count: int, shape, dtype: torch.dtype):
+        """Pairs [first, first + count) of the last refine_membranes call as two (count,Z,H,W) device stacks of `dtype`."""
+        org = torch.empty((count,) + tuple(shape), dtype=dtype, device=self.device)
+        mem = torch.empty_like(org)
+        self._check(self.lib.saber_refine_membranes_instances(self.h, int(first), int(count), org.element_size(), _ptr(org), _ptr(mem), _stream()))
+        return org, mem
+
     def set_precision(self, precision: str):
         """Switch between the handle's 16-bit production arithmetic ("bf16" or "fp16": whichever its weights were converted to) and the
         fp32 exact mode (only on a handle created with precision="exact", which keeps the fp32 weight copies)."""

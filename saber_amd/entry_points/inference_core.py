@@ -8,7 +8,12 @@ copick_utils' own when it is installed), so a maintainer keeps the reference's I
 
 segment_micrograph_core (inference_core.py:100-164) - the per-file body of `saber segment micrographs`: read the micrograph (MRC / TIFF),
 Fourier-crop to the target resolution, run the 2-D segmenter, write image + label stack as one run of the OME-Zarr store (SURVEY.md 8
-row f-4: saber_amd.utils.{mrc,tiff,zarr_v2,zarr_writer})."""
+row f-4: saber_amd.utils.{mrc,tiff,zarr_v2,zarr_writer}).
+
+refine_membranes_core (reference: saber/entry_points/run_membrane_refinement.py:92-130, run_refinement + return_write_user_id) - the per-run
+body of `saber analysis refine-membranes`: read the organelle and the membrane segmentation, refine them on the device
+(saber_amd.analysis.OrganelleMembraneFilter.run_labels: the flattened label maps, without the reference's 4-D detour), write the membrane
+map and then the organelle map under the `-refined` user ids."""
 import logging
 
 import numpy as np
@@ -83,3 +88,38 @@ def segment_micrograph_core(input: str, output: str, scale_factor: float, target
     if out_image.ndim == 3:
         out_image = out_image[:, :, 0]
     zwriter.write(run_name=os.path.splitext(os.path.basename(input))[0], image=out_image, masks=masks, pixel_size=pixel_size)
+
+
+def return_write_user_id(user_id, run=None):
+    """run_membrane_refinement.py:126-130"""
+    return "saber-refined" if user_id is None else user_id + "-refined"
+
+
+def refine_membranes_core(run, org_info, mem_info, voxel_size, save_session_id, refiner, read_segmentation=None, write_segmentation=None):
+    """org_info / mem_info: (name, user_id, session_id) as the reference's CLI passes them.  read_segmentation / write_segmentation: callables
+    with the signatures of copick_utils.io.readers.segmentation / writers.segmentation (the defaults when copick_utils is installed).
+    Returns None when a segmentation is missing, else {'organelles', 'membranes'}: the two saved 3-D label maps (numpy, the organelle
+    input's dtype; organelle v is saved as v + 1, as the reference saves it)."""
+    if read_segmentation is None or write_segmentation is None:
+        try:
+            from copick_utils.io import readers, writers      # the reference's own I/O layer (run_membrane_refinement.py:94)
+        except ImportError as ex:
+            raise ImportError("copick_utils is not installed: pass read_segmentation= / write_segmentation= callables "
+                              "(signatures of copick_utils.io.readers.segmentation / writers.segmentation)") from ex
+        read_segmentation, write_segmentation = read_segmentation or readers.segmentation, write_segmentation or writers.segmentation
+    org_seg = read_segmentation(run, voxel_size, org_info[0], session_id=org_info[2], user_id=org_info[1])
+    mem_seg = read_segmentation(run, voxel_size, mem_info[0], session_id=mem_info[2], user_id=mem_info[1])
+    if org_seg is None:
+        print(f"No Organele Segmentation Found for {run.name}")
+        return None
+    elif mem_seg is None:
+        print(f"No Membrane Segmentation Found for {run.name}")
+        return None
+    org_labels, mem_labels = refiner.run_labels(org_seg, mem_seg)
+    out_dtype = org_seg.dtype if isinstance(org_seg, np.ndarray) else torch.empty(0, dtype=org_seg.dtype).numpy().dtype
+    signed = {torch.uint16: torch.int16, torch.uint32: torch.int32}
+    mem_out = mem_labels.cpu().view(signed.get(mem_labels.dtype, mem_labels.dtype)).numpy().astype(out_dtype)
+    org_out = org_labels.cpu().view(signed.get(org_labels.dtype, org_labels.dtype)).numpy().astype(out_dtype)
+    write_segmentation(run, mem_out, return_write_user_id(mem_info[1], run), name=mem_info[0], session_id=save_session_id, voxel_size=voxel_size)
+    write_segmentation(run, org_out, return_write_user_id(org_info[1], run), name=org_info[0], session_id=save_session_id, voxel_size=voxel_size)
+    return {"organelles": org_out, "membranes": mem_out}
