@@ -313,6 +313,29 @@ int saber_refine_membranes(saber_engine* e, const void* org_dev, int elem_bytes,
 int saber_refine_membranes_instances(saber_engine* e, int first, int count, int elem_bytes, void* org_stack_dev, void* mem_stack_dev,
                                      void* stream);
 
+/* ---- organelle statistics (saber/analysis/organelle_statistics.py), csrc/labelstats.hip.  Only a created handle is needed. ----
+ * What extract_organelle_statistics (organelle_statistics.py:5-79) computes per label, for every label at once: np.unique(mask) > 0
+ * (:15-16), the voxel count np.sum(mask == label) (:22-25, :40) and, of skimage.measure.regionprops on that mask (:30), the centroid (:31)
+ * and axis_major_length / axis_minor_length (:44-45).  The volume is read twice whatever the number of labels (which values are present;
+ * their moments), where the reference makes several passes and a full-volume temporary per label.
+ * labels_dev: (Z,H,W) of elem_bytes 1 (unsigned), 2 or 4, is_signed != 0 for int16 / int32; values <= 0 are background, 32-bit values
+ * lie in 1..2^22, the narrow types may use their whole range.  Z, H, W <= 65535 and Z*H*W < 2^31.
+ * Outputs, K rows in ascending label order, all on the engine's device, each with room for `capacity` rows:
+ *   labels_out_dev   uint32[K]      the label values
+ *   moments_out_dev  uint64[K][16]  n, Sz, Sy, Sx, Szz, Syy, Sxx, Szy, Szx, Syx (sums over the label's voxel coordinates), zmin, ymin,
+ *                                   xmin, zmax, ymax, xmax (inclusive bounding box).  Integer accumulation: exact, the same bits every call.
+ *   stats_out_dev    double[K][8]   centroid z, y, x; axis_major_length = sqrt(20 l0); axis_minor_length = sqrt(20 max(l2, 0)); l0 >= l1 >=
+ *                                   l2, the eigenvalues of the covariance of the voxel coordinates (divided by n, as skimage does).  For a
+ *                                   3-D region skimage's sqrt(10 (ev0 + ev1 - ev2)) and sqrt(10 (-ev0 + ev1 + ev2)) on the inertia tensor's
+ *                                   eigenvalues are exactly these.  A flat label has minor length 0: the reference's equivalent-sphere
+ *                                   fall-back (:52-55), reached only when rounding makes the sqrt argument negative, is not reproduced.
+ * *out_n_labels = K, also when the call fails with SABER_ERR_CAPACITY because K > capacity (nothing is written then; call again with
+ * room for K rows).  The 3-voxel rule (:25) is the caller's: every label > 0 gets a row.  mode 0: moments reduced per block in LDS
+ * before they reach global memory; mode 1: one global update per row piece and label (the baseline mode 0 is measured against; same
+ * results).  Two stream synchronisations per call, whatever K is. */
+int saber_label_statistics(saber_engine* e, const void* labels_dev, int elem_bytes, int is_signed, int Z, int H, int W, int capacity, int mode,
+                           uint32_t* labels_out_dev, uint64_t* moments_out_dev, double* stats_out_dev, int* out_n_labels, void* stream);
+
 /* ---- domain-expert classifier filter on the engine's image embeddings ----
  * Replaces saber.classifier.models.predictor.Predictor (saber/classifier/models/predictor.py:9-60 construction, :117-175 predict) with the
  * SAM2Classifier model (saber/classifier/models/SAM2.py:21-197) behind it; hook: saber2D._apply_classifier -> filters.apply_classifier

@@ -38,6 +38,7 @@ struct saber_engine {
     bool keep_f32 = false;          // fp32 weight copies were requested before finalize (exact mode available)
     void* exact_ws = nullptr;       // exact.hip's workspaces (allocated on first use)
     void* refine_state = nullptr;   // morph3d.hip: ball tables and the pairs of the last saber_refine_membranes call (allocated on first use)
+    void* labelstats_ws = nullptr;  // labelstats.hip: label bitmap, rank table and counters (1 MiB, allocated on first use, freed with allocs)
 
     // model description (tiny / small / base+ / large)
     int embed_dim = 0;

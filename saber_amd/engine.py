@@ -313,6 +313,30 @@ class Engine:
         self._check(self.lib.saber_refine_membranes_instances(self.h, int(first), int(count), org.element_size(), _ptr(org), _ptr(mem), _stream()))
         return org, mem
 
+    # ------------------------------------------------------------------ organelle statistics (csrc/labelstats.hip)
+    def label_statistics(self, labels: torch.Tensor, capacity: int = 1024, per_piece_atomics: bool = False):
+        """Per-label moments of a (Z,H,W) uint8 / (u)int16 / (u)int32 device tensor (include/saber_amd.h: saber_label_statistics).
+        Returns device tensors with one row per label > 0, ascending: (labels int32[K], moments int64[K,16], stats float64[K,8]); the
+        unsigned values of the C-ABI fit the signed types.  `capacity` is a first guess: the call is repeated once with the K it reports.
+        per_piece_atomics selects the unreduced baseline form of the moments kernel (same results, for measurements)."""
+        assert labels.is_cuda and labels.dim() == 3 and labels.is_contiguous()
+        if labels.dtype not in (torch.uint8, torch.int16, torch.uint16, torch.int32, torch.uint32):
+            raise ValueError(f"label_statistics: unsupported label dtype {labels.dtype}")
+        Z, H, W = labels.shape
+        signed = int(labels.dtype in (torch.int16, torch.int32))
+        n = C.c_int(0)
+        while True:
+            lab = torch.empty((capacity,), dtype=torch.int32, device=labels.device)
+            mom = torch.empty((capacity, 16), dtype=torch.int64, device=labels.device)
+            stats = torch.empty((capacity, 8), dtype=torch.float64, device=labels.device)
+            st = self.lib.saber_label_statistics(self.h, _ptr(labels), labels.element_size(), signed, Z, H, W, int(capacity), int(bool(per_piece_atomics)),
+                                                 _ptr(lab), _ptr(mom), _ptr(stats), C.byref(n), _stream())
+            if st == _lib.SABER_ERR_CAPACITY and n.value > capacity:
+                capacity = n.value
+                continue
+            self._check(st)
+            return lab[:n.value], mom[:n.value], stats[:n.value]
+
     def set_precision(self, precision: str):
         """Switch between the handle's 16-bit production arithmetic ("bf16" or "fp16": whichever its weights were converted to) and the
         fp32 exact mode (only on a handle created with precision="exact", which keeps the fp32 weight copies)."""

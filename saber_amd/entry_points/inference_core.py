@@ -13,7 +13,14 @@ row f-4: saber_amd.utils.{mrc,tiff,zarr_v2,zarr_writer}).
 refine_membranes_core (reference: saber/entry_points/run_membrane_refinement.py:92-130, run_refinement + return_write_user_id) - the per-run
 body of `saber analysis refine-membranes`: read the organelle and the membrane segmentation, refine them on the device
 (saber_amd.analysis.OrganelleMembraneFilter.run_labels: the flattened label maps, without the reference's 4-D detour), write the membrane
-map and then the organelle map under the `-refined` user ids."""
+map and then the organelle map under the `-refined` user ids.
+
+organelle_statistics_core / process_organelles_core (reference: saber/entry_points/run_analysis.py:124-156 process_single_run, :35-122
+process_organelles, :185-192 pickable_object_check) - the bodies of `saber analysis save coordinates` / `save statistics`: read the organelle
+segmentation of each run, gather the per-label table on the device (saber_amd.analysis.extract_organelle_statistics), save one pick per
+organelle and write the size statistics as CSV.  The runs are processed one after another on the device; the reference's process pool, the
+copick project layer and the slurm command are not re-implemented."""
+import csv
 import logging
 
 import numpy as np
@@ -123,3 +130,68 @@ def refine_membranes_core(run, org_info, mem_info, voxel_size, save_session_id, 
     write_segmentation(run, mem_out, return_write_user_id(mem_info[1], run), name=mem_info[0], session_id=save_session_id, voxel_size=voxel_size)
     write_segmentation(run, org_out, return_write_user_id(org_info[1], run), name=org_info[0], session_id=save_session_id, voxel_size=voxel_size)
     return {"organelles": org_out, "membranes": mem_out}
+
+
+def organelle_statistics_core(run, organelle_name, session_id, user_id, voxel_size, save_copick, save_statistics, read_segmentation=None,
+                              write_picks=None):
+    """run_analysis.py:124-156.  read_segmentation: a callable with the signature of copick_utils.io.readers.segmentation (the default when
+    copick_utils is installed); write_picks: see saber_amd.analysis.save_coordinates_to_copick.  Returns the run's CSV rows ([] when the
+    segmentation is missing or save_statistics is off)."""
+    from saber_amd.analysis import extract_organelle_statistics
+    if read_segmentation is None:
+        try:
+            from copick_utils.io import readers              # the reference's own I/O layer (run_analysis.py:127)
+        except ImportError as ex:
+            raise ImportError("copick_utils is not installed: pass a read_segmentation= callable "
+                              "(signature of copick_utils.io.readers.segmentation)") from ex
+        read_segmentation = readers.segmentation
+    seg = read_segmentation(run, voxel_size, organelle_name, session_id, user_id)
+    if seg is None:
+        print(f"{run.name} didn't have any {organelle_name} segmentations present!")
+        return []
+    csv_rows = extract_organelle_statistics(run, seg, organelle_name, session_id, user_id, voxel_size, save_copick, save_statistics,
+                                            write_picks=write_picks)
+    return csv_rows if save_statistics and csv_rows else []
+
+
+def pickable_object_check(pickable_objects, organelle_name):
+    """run_analysis.py:185-192.  pickable_objects: a copick root (its .pickable_objects are used) or the list itself."""
+    objects = getattr(pickable_objects, "pickable_objects", pickable_objects)
+    if not any(obj.name == organelle_name for obj in objects):
+        available_names = f"Available pickable object names: {', '.join(obj.name for obj in objects)}"
+        raise ValueError(f"Pickable Object {organelle_name} not found in Config!\n{available_names}")
+
+
+def process_organelles_core(runs, organelle_name, session_id, user_id, voxel_size, save_copick=True, save_statistics=True, output="statistics.csv",
+                            *, pickable_objects=None, read_segmentation=None, write_picks=None):
+    """run_analysis.py:35-122 without the project layer: `runs` are the run objects.  Writes `output` with the reference's header and appends
+    the rows of all runs, in run order, when there are any.  With save_copick the organelle must be among `pickable_objects` (a copick root or
+    its list of objects).  Returns all CSV rows."""
+    if not save_copick and not save_statistics:
+        raise ValueError("At least one of save_copick or save_statistics must be True")
+    if save_copick:
+        if pickable_objects is None:
+            raise ValueError("save_copick needs pickable_objects= (the copick root or its pickable objects) for the pickable-object check")
+        pickable_object_check(pickable_objects, organelle_name)
+    if save_statistics:
+        with open(output, "w", newline="") as csvfile:
+            csv.writer(csvfile).writerow(["run_id", "label", "volume_nm3", "diameter_nm"])
+    all_csv_rows = []
+    for run in runs:
+        csv_rows = organelle_statistics_core(run, organelle_name, session_id, user_id, voxel_size, save_copick, save_statistics,
+                                             read_segmentation=read_segmentation, write_picks=write_picks)
+        if csv_rows:
+            all_csv_rows.extend(csv_rows)
+    if save_statistics and all_csv_rows:
+        with open(output, "a", newline="") as csvfile:
+            writer = csv.writer(csvfile)
+            for row in all_csv_rows:
+                writer.writerow(row)
+        print(f"\nStatistics saved to {output}")
+    completion_msg = []
+    if save_copick:
+        completion_msg.append("Coordinate extraction")
+    if save_statistics:
+        completion_msg.append("Statistics calculation")
+    print(f"{' and '.join(completion_msg)} complete!")
+    return all_csv_rows
