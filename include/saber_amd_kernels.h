@@ -112,6 +112,21 @@ int saber_k_flash256(const uint16_t* Q, const uint16_t* K, const uint16_t* V, in
 /* one axis (0: rows, 1: columns) of scipy.ndimage.gaussian_filter(sigma, mode="mirror", truncate=4) on n planes of H x W: the anti-aliasing filter
  * skimage.transform.resize applies before it down-samples a tomogram slice to the model's 1024 px (saber/adapters/preprocessing.py:21) */
 int saber_k_gauss_mirror(const float* in, float* out, int n_planes, int H, int W, int axis, double sigma, void* stream);
+/* ---- slab preparation of tomoSegmenter.segment_vol (saber/segmenters/tomo.py:98-101; csrc/volprep.hip) */
+/* 1-D correlation along `len` of a contiguous (outer, len, inner) array with zero ("same") padding: scipy.ndimage.correlate1d(mode="constant"),
+ * the conv1d of saber.filters.gaussian.gaussian_smoothing.  out[o][l][i] = sum_k taps[k] * in[o][l + k - ks/2][i], fp32 fma chain in ascending
+ * k starting from 0.  in: dtype 0 float32, 1 int16, 2 uint16, 3 uint8 (widened exactly); out: fp32, a separate buffer (in is never written).
+ * taps_host: ks HOST floats, ks odd, 3..63 (15 = sigma 5 is the tuned case).  chunk_len: outputs per thread along `len` in the ks = 15
+ * kernel for inner > 1 (rounded up to a multiple of 8), 0 = chosen from the shape.  minmax_dev (optional): two device floats that receive
+ * min and max of everything written to out (NaNs are ignored), in the same pass. */
+int saber_k_correlate1d_zero(const void* in, int dtype, float* out, int64_t outer, int64_t len, int64_t inner, const float* taps_host, int ks,
+                             int chunk_len, float* minmax_dev, void* stream);
+/* preprocess.normalize(rgb=False) in place: v = (v - lo) / ((hi - lo) + 1e-8f) with lo = minmax_dev[0], hi = minmax_dev[1] read on the device;
+ * fp32 subtraction, addition and IEEE division, one rounding each */
+int saber_k_normalize_minmax(float* v, int64_t n, const float* minmax_dev, void* stream);
+/* preprocess.project_tomogram: out (H,W) = (vol[z0] + vol[z0+1] + ... + vol[z1-1]) / float(z1 - z0), fp32 sum in ascending z, then one IEEE division
+ * (numpy's mean over axis 0); 0 <= z0 < z1 <= Z, an empty range is refused */
+int saber_k_project_mean(const float* vol, int Z, int H, int W, int z0, int z1, float* out, void* stream);
 /* out = x + alpha * g[c] * y  (x, g may be NULL) */
 int saber_k_axpy(const float* x, const float* y, const float* g, float alpha, int64_t rows, int C, float* out, void* stream);
 /* out = x + y[row % y_rows] as bf16 and/or fp32 (y may be NULL) */

@@ -148,6 +148,9 @@ SIGNATURES = {
     "saber_k_ln_mx": (_i, [_vp, C.c_int64, _vp, _vp, _f, _i, _vp, C.c_int64, _i, _vp, C.c_int64, C.c_int64, _vp]),
     "saber_k_flash256": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, C.c_int64, _vp]),
     "saber_k_gauss_mirror": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp]),
+    "saber_k_correlate1d_zero": (_i, [_vp, _i, _vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_float), _i, _i, _vp, _vp]),
+    "saber_k_normalize_minmax": (_i, [_vp, C.c_int64, _vp, _vp]),
+    "saber_k_project_mean": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "saber_k_axpy": (_i, [_vp, _vp, _vp, _f, C.c_int64, _i, _vp, _vp]),
     "saber_k_add_to_bf16": (_i, [_vp, _vp, _i, _vp, _vp, C.c_int64, _i, _vp]),
     "saber_k_bf16_to_f32": (_i, [_vp, C.c_int64, _vp, _vp]),

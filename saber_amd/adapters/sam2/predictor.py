@@ -69,10 +69,11 @@ class SAM2Adapter(BaseAdapter):
         return self._video_predictor
 
     @torch.inference_mode()
-    def set_volume(self, tomogram: np.ndarray, offload_video_to_cpu: bool = False) -> None:
-        """predictor.py:76-86: normalise the tomogram, resize every slice to the model's 1024^2, start an empty inference state"""
+    def set_volume(self, tomogram, offload_video_to_cpu: bool = False) -> None:
+        """predictor.py:76-86: normalise the tomogram, resize every slice to the model's 1024^2, start an empty inference state.
+        tomogram: (Z,H,W) numpy, or a CUDA float32 tensor, which is used where it lies"""
         from saber_amd.adapters.sam2.video import load_tomogram_frames_device
-        self._vol_shape = tomogram.shape
+        self._vol_shape = tuple(tomogram.shape)
         self.frame_metrics = {}
         vp = self._video()
         frames = load_tomogram_frames_device(tomogram, vp.lib, vp.dev, 1024, self._config.light_modality)

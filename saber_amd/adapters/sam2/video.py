@@ -129,11 +129,17 @@ def load_tomogram_frames(tomogram: np.ndarray, image_size: int = 1024, light_mod
     return out
 
 
-def load_tomogram_frames_device(tomogram: np.ndarray, lib, device, image_size: int = 1024, light_modality: bool = False) -> torch.Tensor:
+def load_tomogram_frames_device(tomogram, lib, device, image_size: int = 1024, light_modality: bool = False) -> torch.Tensor:
     """load_tomogram_frames on the device: the two affine steps (min-max to [-1,1], then 2x - 1) commute with the bilinear resize, so the
     volume is uploaded once and one resize launch with the fused affine map v -> 4 (v - min) / (max - min) - 3 produces the (Z, 1024, 1024)
-    frame stack in HBM (the host version spends ~25 ms per slice in numpy); tomograms larger than 1024 px go through the Gaussian filter first."""
-    t = torch.from_numpy(np.ascontiguousarray(tomogram, dtype=np.float32)).to(device)
+    frame stack in HBM (the host version spends ~25 ms per slice in numpy); tomograms larger than 1024 px go through the Gaussian filter first.
+    A CUDA float32 tensor (what tomoSegmenter's device preparation hands over) is read where it lies and is not modified."""
+    if isinstance(tomogram, torch.Tensor):
+        if not tomogram.is_cuda or tomogram.dtype != torch.float32 or tomogram.dim() != 3:
+            raise TypeError("load_tomogram_frames_device: a tensor tomogram must be a (Z,H,W) CUDA float32 tensor")
+        t = tomogram.to(device).contiguous()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(tomogram, dtype=np.float32)).to(device)
     Z, H, W = t.shape
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     mn, mx = (float(v) for v in torch.aminmax(t))              # of the tomogram as loaded: the reference normalises before it resizes

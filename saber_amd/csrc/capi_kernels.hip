@@ -304,6 +304,17 @@ extern "C" int saber_k_gauss_mirror(const float* in, float* out, int n_planes, i
 extern "C" int saber_k_axpy(const float* x, const float* y, const float* g, float alpha, int64_t rows, int C, float* out, void* stream) {
     return kcheck(launch_axpy(x, y, g, alpha, rows, C, out, (hipStream_t)stream));
 }
+// slab preparation (volprep.hip)
+extern "C" int saber_k_correlate1d_zero(const void* in, int dtype, float* out, int64_t outer, int64_t len, int64_t inner, const float* taps_host, int ks,
+                                        int chunk_len, float* minmax_dev, void* stream) {
+    return kcheck(launch_correlate1d_zero(in, dtype, out, outer, len, inner, taps_host, ks, chunk_len, minmax_dev, (hipStream_t)stream));
+}
+extern "C" int saber_k_normalize_minmax(float* v, int64_t n, const float* minmax_dev, void* stream) {
+    return kcheck(launch_normalize_minmax(v, n, minmax_dev, (hipStream_t)stream));
+}
+extern "C" int saber_k_project_mean(const float* vol, int Z, int H, int W, int z0, int z1, float* out, void* stream) {
+    return kcheck(launch_project_mean(vol, Z, H, W, z0, z1, out, (hipStream_t)stream));
+}
 extern "C" int saber_k_add_to_bf16(const float* x, const float* y, int y_rows, uint16_t* out_bf16, float* out_f32, int64_t rows, int C, void* stream) {
     return kcheck(launch_add_to_bf16(x, y, y_rows, out_bf16, out_f32, rows, C, (hipStream_t)stream));
 }

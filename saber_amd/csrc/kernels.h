@@ -87,6 +87,13 @@ struct LayerNormParams {
 const char* launch_prepare_u16(const uint16_t* img, int H, int W, float* out, float* ws, unsigned int* minmax, hipStream_t s);
 const char* launch_prepare_f32(const float* img, int H, int W, float* out, float* ws, unsigned int* minmax, hipStream_t s);
 const char* launch_prepare_rgb_f32(const float* img, int H, int W, float* out, float* ws, unsigned int* minmax, hipStream_t s);   // (H,W,3) interleaved
+// ------------------------------------------------------------------ volprep.hip: slab preparation (z Gaussian + min/max, normalise, projection)
+#define VP_MAX_KS 63
+// dtype: 0 float32, 1 int16, 2 uint16, 3 uint8; taps: ks host floats; chunk_len: 0 = automatic; minmax: 2 device floats or NULL
+const char* launch_correlate1d_zero(const void* in, int dtype, float* out, int64_t outer, int64_t len, int64_t inner, const float* taps, int ks,
+                                    int chunk_len, float* minmax, hipStream_t s);
+const char* launch_normalize_minmax(float* v, int64_t n, const float* minmax, hipStream_t s);
+const char* launch_project_mean(const float* vol, int Z, int H, int W, int z0, int z1, float* out, hipStream_t s);
 const char* launch_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res,
                                     hipStream_t s);
 const char* launch_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images,

@@ -40,7 +40,9 @@ def _copick_io():
 
 def segment_tomogram_core(run, voxel_size: float, tomogram_algorithm: str, segmentation_name: str, segmentation_session_id: str,
                           slab_thickness: int, num_slabs: int, delta_z: int, display_segmentation: bool, segmenter, gpu_id: int = 0,
-                          target_class: int = 1, *, read_tomogram=None, write_segmentation=None):
+                          target_class: int = 1, *, read_tomogram=None, write_segmentation=None, device_prep: bool = False):
+    """device_prep: upload the tomogram once and let the segmenter prepare it on the device (smoothing, normalisation, projection:
+    saber_amd/utils/volprep.py); False keeps the host preparation of the reference."""
     logger = logging.getLogger(__name__)
     if read_tomogram is None or write_segmentation is None:
         rd, wr = _copick_io()
@@ -51,6 +53,9 @@ def segment_tomogram_core(run, voxel_size: float, tomogram_algorithm: str, segme
         return None
     torch.cuda.set_device(gpu_id)
     img_name = run.name + "-" + segmentation_session_id
+    if device_prep:
+        from saber_amd.utils.volprep import to_device_volume
+        vol = to_device_volume(vol, torch.device("cuda", gpu_id))
     if num_slabs > 1:
         segment_mask = segmenter.segment(vol, slab_thickness, num_slabs, delta_z, img_name, display_segmentation)
     else:

@@ -1,7 +1,9 @@
 """tomoSegmenter (reference: saber/segmenters/tomo.py:14-139).  segment_slab's 2-D path (z-smoothing -> normalise ->
 slab projection -> segment_image) feeds segment_vol, which continues into SAM2 video propagation on the engine
-(SAM2Adapter.segment_volume, saber_amd/adapters/sam2/video.py).  The z Gaussian (filters/gaussian.py:17-74, sigma 5, conv1d) is host
-glue outside the per-slice loop and is evaluated with scipy's separable filter of the same kernel."""
+(SAM2Adapter.segment_volume, saber_amd/adapters/sam2/video.py).  The z Gaussian (filters/gaussian.py:17-74, sigma 5, conv1d) is
+glue outside the per-slice loop.  For a numpy volume it is host glue, evaluated with scipy's separable filter of the same kernel; for a
+CUDA tensor (float32, int16, uint16, uint8) the whole preparation runs on the device (saber_amd/utils/volprep.py, csrc/volprep.hip):
+smoothing with fused min / max, normalisation in place, projection - and the volume goes to the video path where it lies."""
 from typing import Optional
 
 import numpy as np
@@ -11,15 +13,8 @@ from saber_amd.adapters.base import AdapterConfig
 from saber_amd.adapters.sam2.amg import cfgAMG
 from saber_amd.segmenters.base import saber3D
 from saber_amd.utils import preprocessing as preprocess
-
-
-def make_gaussian_kernel(sigma: float) -> np.ndarray:
-    """Kernel of the reference (filters/gaussian.py:7-15): odd size max(round(3 sigma), 3), taps on linspace(-ks/2, ks/2, ks)."""
-    ks = max(round(sigma * 3), 3)
-    ks += 1 - ks % 2
-    ts = np.linspace(-ks / 2, ks / 2, ks, dtype=np.float32)
-    g = np.exp(-(ts / np.float32(sigma)) ** 2 / 2).astype(np.float32)
-    return g / g.sum()
+from saber_amd.utils import volprep
+from saber_amd.utils.volprep import make_gaussian_kernel
 
 
 def gaussian_smoothing_z(vol: np.ndarray, sigma: float, dim: int = 0) -> np.ndarray:
@@ -36,7 +31,14 @@ class tomoSegmenter(saber3D):
     @torch.inference_mode()
     def segment_slab(self, vol, slab_thickness: int = 10, zSlice: Optional[int] = None, display: bool = True,
                      text: Optional[str] = None, target_class: Optional[int] = 1):
-        self.vol = preprocess.normalize(gaussian_smoothing_z(vol, 5, dim=0))
+        if isinstance(vol, torch.Tensor):
+            if not volprep.is_device_volume(vol) or vol.dim() != 3:
+                raise TypeError("segment_slab: a tensor volume must be a (Z,H,W) CUDA tensor of float32, int16, uint16 or uint8")
+            # the smoothed copy is this segmenter's own, so it is normalised in place; `vol` itself is only read
+            smoothed, minmax = volprep.correlate1d_zero(vol, make_gaussian_kernel(5), dim=0, minmax=True)
+            self.vol = preprocess.normalize_(smoothed, minmax)
+        else:
+            self.vol = preprocess.normalize(gaussian_smoothing_z(vol, 5, dim=0))
         if zSlice is None:
             zSlice = int(self.vol.shape[0] // 2)
         self.image0 = preprocess.project_tomogram(self.vol, zSlice, slab_thickness)

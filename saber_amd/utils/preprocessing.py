@@ -2,14 +2,28 @@
 
 `prepare` (contrast + min-max, :67-80) runs on the device through the engine's K0 kernel - it is part of the
 hot path and has no host implementation here.  `normalize` (:20-37) and `project_tomogram` (:39-65) are
-volume-level host glue outside the per-slice loop and stay numpy, like the reference."""
+volume-level glue outside the per-slice loop: numpy input stays numpy, like the reference; a CUDA float32 tensor runs
+the device kernels of saber_amd.utils.volprep (csrc/volprep.hip) and a tensor comes back."""
 from typing import Optional
 
 import numpy as np
 import torch
 
 
+def normalize_(image: torch.Tensor, minmax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`normalize` of a CUDA float32 tensor IN PLACE (what tomoSegmenter uses on its own smoothed volume); `minmax`: its (min, max) as two
+    device floats when the caller already has them (the smoothing kernel leaves them), else torch.aminmax"""
+    from saber_amd.utils import volprep
+    if minmax is None:
+        minmax = torch.stack(torch.aminmax(image))
+    return volprep.normalize_minmax_(image, minmax)
+
+
 def normalize(image: np.ndarray, rgb: bool = False) -> np.ndarray:
+    if isinstance(image, torch.Tensor):
+        if rgb or not image.is_cuda or image.dtype != torch.float32:
+            raise TypeError("normalize: tensor input must be a CUDA float32 tensor with rgb=False")
+        return normalize_(image.clone(memory_format=torch.contiguous_format))
     if rgb:
         lo = image.min(axis=(0, 1), keepdims=True)
         hi = image.max(axis=(0, 1), keepdims=True)
@@ -19,6 +33,17 @@ def normalize(image: np.ndarray, rgb: bool = False) -> np.ndarray:
 
 
 def project_tomogram(vol, zSlice: Optional[int] = None, deltaZ: Optional[int] = None):
+    if isinstance(vol, torch.Tensor):
+        if not vol.is_cuda or vol.dtype != torch.float32 or vol.dim() != 3:
+            raise TypeError("project_tomogram: tensor input must be a (Z,H,W) CUDA float32 tensor")
+        from saber_amd.utils import volprep
+        Z = vol.shape[0]
+        if zSlice is None:
+            return volprep.project_mean(vol, 0, Z)
+        if deltaZ is None:
+            z = int(zSlice) + Z if zSlice < 0 else int(zSlice)
+            return volprep.project_mean(vol, z, z + 1)
+        return volprep.project_mean(vol, int(max(zSlice - deltaZ, 0)), int(min(zSlice + deltaZ, Z)))
     if zSlice is None:
         return np.mean(vol, axis=0)
     if deltaZ is None:
