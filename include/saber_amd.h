@@ -27,6 +27,8 @@
  *   saber_smooth_labels / saber_gaussian_smoothing_3d
  *       <- fast_3d_gaussian_smoothing(volume, scale, deviceID)        saber/filters/masks.py:230-287
  *          gaussian_smoothing_3d(volume, sigma, device)               saber/filters/gaussian.py:76-138
+ *   saber_consensus_components
+ *       <- _consensus_based_resolution(image_shape, masks, confidences) saber/filters/masks.py:64-121
  *
  * Conventions: plain pointers and sizes only; every *_dev pointer is device memory owned by the
  * caller (e.g. a PyTorch-ROCm tensor's data_ptr()); `stream` is a hipStream_t (NULL = default
@@ -335,6 +337,30 @@ int saber_refine_membranes_instances(saber_engine* e, int first, int count, int 
  * results).  Two stream synchronisations per call, whatever K is. */
 int saber_label_statistics(saber_engine* e, const void* labels_dev, int elem_bytes, int is_signed, int Z, int H, int W, int capacity, int mode,
                            uint32_t* labels_out_dev, uint64_t* moments_out_dev, double* stats_out_dev, int* out_n_labels, void* stream);
+
+/* ---- consensus mask resolution (saber/filters/masks.py:64-121), csrc/consensus2d.hip.  Only a created handle is needed. ----
+ * What _consensus_based_resolution computes from the candidate masks of the wanted class, without its per-mask and per-component passes
+ * over the image: the overlap-averaged confidence of every pixel, the 4-connected components (scipy.ndimage.label's default 2-D
+ * structure) of the union of the masks and, per component, area, bounding box and the sum of the averaged confidence.
+ * masks_dev: (n,H,W) uint8 on the engine's device, non-zero = set.  select_host: k row indices into the stack (0 <= index < n, repeats
+ * allowed), conf_host: their k float32 confidences; both HOST arrays, read before the call returns.  H, W >= 1, H*W < 2^31, 1 <= k <= n.
+ * Arithmetic, per pixel: cm = the float32 sum of the confidences of the set masks, added one after the other in list order (the
+ * reference's `confidence_map += seg * conf`), count = the number of set masks, avg = (double)cm / (double)count (0 where count = 0).
+ * Outputs, on the engine's device, allocated by the caller:
+ *   labels_out_dev  int32[H][W]   0 = background, components 1..K numbered in raster order of their first pixel (scipy's order)
+ *   table_out_dev   saber_consensus_row[capacity], rows 0..K-1 written, row i = component i + 1
+ * *out_n_components = K, also when the call fails with SABER_ERR_CAPACITY because K > capacity (labels_out_dev is complete then, the
+ * table is not; call again with room for K rows - ceil(H*W / 2) rows always suffice).  Integer fields are exact and the same every call;
+ * avg_sum is accumulated with fp64 atomics, one add per row run, so its last bits can differ between two calls (relative error within
+ * area * 2^-53 of the exact sum either way).  SABER_ERR_INVALID (checked before anything is launched) for a limit above or a NULL
+ * pointer.  One stream synchronisation per call, whatever k and K are; no (n,H,W)-sized temporary. */
+typedef struct saber_consensus_row {
+    int32_t area, x_min, y_min, x_max, y_max, reserved;   /* inclusive bounds; reserved = 0 */
+    double avg_sum;                                        /* sum of avg over the component's pixels; score = avg_sum / area */
+} saber_consensus_row;
+int saber_consensus_components(saber_engine* e, const uint8_t* masks_dev, int n, int H, int W, const int* select_host, const float* conf_host,
+                               int k, int capacity, int32_t* labels_out_dev, saber_consensus_row* table_out_dev, int* out_n_components,
+                               void* stream);
 
 /* ---- domain-expert classifier filter on the engine's image embeddings ----
  * Replaces saber.classifier.models.predictor.Predictor (saber/classifier/models/predictor.py:9-60 construction, :117-175 predict) with the

@@ -337,6 +337,55 @@ class Engine:
             self._check(st)
             return lab[:n.value], mom[:n.value], stats[:n.value]
 
+    # ------------------------------------------------------------------ consensus mask resolution (csrc/consensus2d.hip)
+    # one row of the C-ABI's saber_consensus_row table as the host reads it
+    CONSENSUS_ROW = np.dtype([("area", np.int32), ("x_min", np.int32), ("y_min", np.int32), ("x_max", np.int32), ("y_max", np.int32),
+                              ("reserved", np.int32), ("avg_sum", np.float64)])
+
+    def consensus_components(self, masks_u8: torch.Tensor, select: Sequence[int], conf, capacity: Optional[int] = None):
+        """4-connected components of the union of the selected masks and their consensus table (include/saber_amd.h:
+        saber_consensus_components).  masks_u8: (n,H,W) uint8 device tensor, non-zero = set; select: k row indices in list order; conf:
+        their k confidences (cast to float32).  Returns (labels, table): labels is the (H,W) int32 device tensor, 0 = background and
+        1..K in scipy.ndimage.label's order; table maps "area", "x_min", "y_min", "x_max", "y_max" (int64 numpy arrays) and "score"
+        (float64: the component's mean overlap-averaged confidence) to K entries, ascending label.  `capacity` is a first guess of K
+        (default: ceil(H W / 2) rows, which always suffice, at most 65536); the call is repeated once with the K it reports.
+        Two host synchronisations: the end of the device work, and the download of the table."""
+        if not isinstance(masks_u8, torch.Tensor) or not masks_u8.is_cuda:
+            raise ValueError("consensus_components: the mask stack must be a device tensor")
+        if masks_u8.dtype != torch.uint8 or masks_u8.dim() != 3:
+            raise ValueError(f"consensus_components: the mask stack must be (n,H,W) uint8, got {tuple(masks_u8.shape)} {masks_u8.dtype}")
+        if masks_u8.device != self.device:
+            raise ValueError(f"consensus_components: the mask stack is on {masks_u8.device}, the engine on {self.device}")
+        masks_u8 = masks_u8.contiguous()
+        sel = np.ascontiguousarray(np.asarray(select, dtype=np.int64).reshape(-1))
+        cf = np.ascontiguousarray(np.asarray(conf).reshape(-1).astype(np.float32))
+        n, H, W = masks_u8.shape
+        if sel.size != cf.size:
+            raise ValueError(f"consensus_components: {sel.size} selected masks, {cf.size} confidences")
+        if sel.size == 0 or sel.size > n or sel.min() < 0 or sel.max() >= n or n == 0 or H == 0 or W == 0 or H * W >= 2 ** 31 - 1:
+            raise ValueError(f"consensus_components: a selection of 1..n rows of a non-empty (n,H,W) stack with H W < 2^31 is needed, got "
+                             f"{sel.size} of {tuple(masks_u8.shape)}")
+        sel = sel.astype(np.int32)
+        if capacity is None:
+            capacity = min((H * W + 1) // 2, 65536)
+        labels = torch.empty((H, W), dtype=torch.int32, device=masks_u8.device)
+        k = C.c_int(0)
+        with torch.cuda.device(self.device):
+            while True:
+                table = torch.empty((max(int(capacity), 1), self.CONSENSUS_ROW.itemsize), dtype=torch.uint8, device=masks_u8.device)
+                st = self.lib.saber_consensus_components(self.h, _ptr(masks_u8), n, H, W, sel.ctypes.data_as(C.POINTER(C.c_int)),
+                                                         cf.ctypes.data_as(C.POINTER(C.c_float)), int(sel.size), int(capacity), _ptr(labels),
+                                                         _ptr(table), C.byref(k), _stream())
+                if st == _lib.SABER_ERR_CAPACITY and k.value > capacity:
+                    capacity = k.value
+                    continue
+                self._check(st)
+                break
+        rows = table[:k.value].cpu().numpy().view(self.CONSENSUS_ROW).reshape(-1)
+        out = {name: rows[name].astype(np.int64) for name in ("area", "x_min", "y_min", "x_max", "y_max")}
+        out["score"] = rows["avg_sum"] / np.maximum(rows["area"], 1).astype(np.float64)
+        return labels, out
+
     def set_precision(self, precision: str):
         """Switch between the handle's 16-bit production arithmetic ("bf16" or "fp16": whichever its weights were converted to) and the
         fp32 exact mode (only on a handle created with precision="exact", which keeps the fp32 weight copies)."""

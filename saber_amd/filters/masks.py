@@ -52,17 +52,25 @@ def fast_3d_gaussian_smoothing(volume, scale=0.075, deviceID=None):
 
 
 # ------------------------------------------------------------------------------------------------ classifier filter
-def apply_classifier(image, masks, classifier, desired_class: int = None, min_mask_area: int = 100, batchsize: int = 32):
+def apply_classifier(image, masks, classifier, desired_class: int = None, min_mask_area: int = 100, batchsize: int = 32, *, device=None):
     """saber/filters/masks.py:8-21: class probabilities of every candidate mask (the device part, Predictor.batch_predict), then
-    the host resolution below."""
+    the resolution below.  device (keyword, default None = the host resolution): a ROCm device; the uint8 stack is uploaded once and
+    the same tensor serves the classifier and the device resolution (csrc/consensus2d.hip)."""
     segs = np.array([m["segmentation"].astype(np.uint8) for m in masks])
-    predictions = classifier.batch_predict(image, segs, batchsize)
-    return convert_predictions_to_masks(predictions, masks, desired_class, min_mask_area)
+    if device is None:
+        predictions = classifier.batch_predict(image, segs, batchsize)
+        return convert_predictions_to_masks(predictions, masks, desired_class, min_mask_area)
+    eng = _device_engine(device)
+    stack = torch.from_numpy(np.ascontiguousarray(segs)).to(eng.device) if segs.ndim == 3 else None
+    predictions = classifier.batch_predict(image, segs if stack is None else stack, batchsize)
+    return convert_predictions_to_masks(predictions, masks, desired_class, min_mask_area, device=device, masks_dev=stack)
 
 
-def convert_predictions_to_masks(predictions, masks, desired_class: int = None, min_mask_area: int = 100):
+def convert_predictions_to_masks(predictions, masks, desired_class: int = None, min_mask_area: int = 100, *, device=None, masks_dev=None):
     """saber/filters/masks.py:23-62.  desired_class > 0: the masks predicted as that class, merged where they overlap
-    (_consensus_based_resolution), area-filtered, ascending area.  Otherwise one merged mask per non-background class."""
+    (_consensus_based_resolution), area-filtered, ascending area.  Otherwise one merged mask per non-background class.
+    device / masks_dev (keywords): run the resolution on that ROCm device; masks_dev is the (n,H,W) uint8 stack of ALL the masks, row i =
+    masks[i], when the caller has it on the device already."""
     if isinstance(masks, np.ndarray):
         masks = masks_to_list(masks)
     predicted = np.argmax(predictions, axis=1)
@@ -72,7 +80,9 @@ def convert_predictions_to_masks(predictions, masks, desired_class: int = None, 
         masks = [masks[i] for i in idx]
         conf = conf[idx]
         if len(masks) > 0:
-            masks = _consensus_based_resolution(masks[0]["segmentation"].shape, masks, conf)
+            # the area filter is handed down: a component below it is dropped before its full-size array is built
+            masks = _consensus_based_resolution(masks[0]["segmentation"].shape, masks, conf, device=device, masks_dev=masks_dev,
+                                                select=None if masks_dev is None else idx, min_area=min_mask_area)
             masks = sorted([m for m in masks if m["area"] >= min_mask_area], key=lambda m: m["area"], reverse=False)
         return masks
     if len(masks) == 0:
@@ -80,9 +90,18 @@ def convert_predictions_to_masks(predictions, masks, desired_class: int = None, 
     return _semantic_segmentation(masks, predictions)
 
 
-def _consensus_based_resolution(image_shape, masks, confidences):
+def _component_entry(comp, area, x0, y0, x1, y1, score):
+    return {"segmentation": comp, "area": area, "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": score,
+            "point_coords": [[int((x0 + x1) / 2), int((y0 + y1) / 2)]], "stability_score": score, "crop_box": [x0, y0, x1, y1]}
+
+
+def _consensus_based_resolution(image_shape, masks, confidences, *, device=None, masks_dev=None, select=None, min_area=0):
     """saber/filters/masks.py:64-122: connected components of the union of the masks; each component's score is the mean, over its
-    pixels, of the overlap-averaged class confidence."""
+    pixels, of the overlap-averaged class confidence.  Keywords: device = a ROCm device runs the arithmetic there
+    (_consensus_on_device; None = this host code); masks_dev = an (n,H,W) uint8 device stack to use instead of uploading the
+    segmentations, select = the rows of it that `masks` are (default 0..len(masks)-1); min_area drops smaller components."""
+    if device is not None:
+        return _consensus_on_device(image_shape, masks, confidences, device, masks_dev, select, min_area)
     from scipy import ndimage
     h, w = image_shape
     conf_map = np.zeros((h, w), dtype=np.float32)
@@ -96,11 +115,62 @@ def _consensus_based_resolution(image_shape, masks, confidences):
     out = []
     for lab in range(1, ncomp + 1):
         comp = labeled == lab
+        area = int(np.sum(comp))
+        if area < min_area:
+            continue
         score = float(np.mean(avg[comp]))
         ys, xs = np.where(comp)
         y0, y1, x0, x1 = int(ys.min()), int(ys.max()), int(xs.min()), int(xs.max())
-        out.append({"segmentation": comp, "area": int(np.sum(comp)), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": score,
-                    "point_coords": [[int((x0 + x1) / 2), int((y0 + y1) / 2)]], "stability_score": score, "crop_box": [x0, y0, x1, y1]})
+        out.append(_component_entry(comp, area, x0, y0, x1, y1, score))
+    return out
+
+
+def _device_engine(device):
+    """The filters' handle on `device`; without a ROCm device this is the package's "no CPU fallback" error."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"the device consensus resolution needs a ROCm device, got device={device!r} and torch.cuda.is_available() is "
+                           "False; there is no CPU fallback (leave `device` unset for the host resolution)")
+    return handle(device)
+
+
+def _consensus_on_device(image_shape, masks, confidences, device, masks_dev, select, min_area):
+    """The device route of _consensus_based_resolution (Engine.consensus_components, csrc/consensus2d.hip): the same dict list, built
+    from the component table and the downloaded label plane.  A float64 confidence is cast to float32, the type the reference's
+    float32 `confidence_map +=` accumulates in."""
+    h, w = (int(v) for v in image_shape)
+    conf = np.asarray(confidences, dtype=np.float32).reshape(-1)
+    k = len(masks) if select is None else len(select)
+    if conf.size != k:
+        raise ValueError(f"_consensus_based_resolution: {k} selected masks, {conf.size} confidences")
+    if masks_dev is None and select is not None:
+        raise ValueError("_consensus_based_resolution: `select` indexes `masks_dev`, which is missing")
+    if masks_dev is not None and (not isinstance(masks_dev, torch.Tensor) or masks_dev.dim() != 3 or tuple(masks_dev.shape[1:]) != (h, w)):
+        raise ValueError(f"_consensus_based_resolution: masks_dev must be an (n, {h}, {w}) device tensor")
+    if masks_dev is None:
+        for m in masks:
+            if tuple(m["segmentation"].shape) != (h, w):
+                raise ValueError(f"_consensus_based_resolution: a mask of shape {tuple(m['segmentation'].shape)} in an image of {(h, w)}")
+    if k == 0:
+        return []
+    eng = _device_engine(device)
+    if masks_dev is None:
+        stack = np.empty((k, h, w), dtype=np.uint8)
+        for j, m in enumerate(masks):
+            stack[j] = m["segmentation"]
+        masks_dev = torch.from_numpy(stack).to(eng.device)
+    labels, table = eng.consensus_components(masks_dev, range(k) if select is None else select, conf)
+    if table["area"].size == 0:
+        return []
+    plane = labels.cpu().numpy()
+    out = []
+    for i in range(table["area"].size):
+        area = int(table["area"][i])
+        if area < min_area:
+            continue
+        x0, y0, x1, y1 = int(table["x_min"][i]), int(table["y_min"][i]), int(table["x_max"][i]), int(table["y_max"][i])
+        comp = np.zeros((h, w), dtype=bool)
+        comp[y0:y1 + 1, x0:x1 + 1] = plane[y0:y1 + 1, x0:x1 + 1] == i + 1
+        out.append(_component_entry(comp, area, x0, y0, x1, y1, float(table["score"][i])))
     return out
 
 

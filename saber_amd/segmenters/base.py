@@ -33,6 +33,7 @@ class saber2D:
         self.masks = []
         self.save_button = False
         self.remove_repeating_masks = True
+        self.device_consensus = False       # True: the classifier filter's consensus resolution runs on self.device (filters/masks.py, csrc/consensus2d.hip)
 
     def segment(self, image: np.ndarray, target_class: Optional[int] = None, text: Optional[str] = None,
                 threshold: Optional[float] = 0.5, display: bool = False, use_sliding_window: bool = False) -> list:
@@ -75,6 +76,8 @@ class saber2D:
         gray = image[:, :, 0] if image.ndim == 3 else image
         # (positional arguments as in the reference, base.py:172-174: self.batchsize lands in apply_classifier's min_mask_area slot and
         # the group size stays at its default of 32)
+        if self.device_consensus:
+            return filters.apply_classifier(gray, masks, self.classifier, self.target_class, self.batchsize, device=self.device)
         return filters.apply_classifier(gray, masks, self.classifier, self.target_class, self.batchsize)
 
     def get_sliding_windows(self, image_shape: Tuple[int, int]) -> List[Tuple[int, int, int, int]]:
