@@ -76,6 +76,25 @@ int saber_k_conv3x3s2_t(const float* in, int H, int W, int Cin, const float* wt,
 /* plane[y][x] = label wherever logits (Hv,Wv) > thr at the nearest source pixel of the output pixel centre; any_flag (optional, device
  * int) is OR-ed with 1 when a pixel was painted.  SAM2Adapter.segment_volume's _apply, saber/adapters/sam2/predictor.py:288-298. */
 int saber_k_paint_nearest(const float* logits, int Hv, int Wv, float thr, int label, uint16_t* plane, int H, int W, int* any_flag, void* stream);
+/* ---- propagated label volumes (csrc/labelvol.hip): what lies between the tracking loop and the 3-D stitch, without leaving the device */
+/* All n objects of a frame in one launch, bit-identical to n saber_k_paint_nearest calls in list order: an output pixel takes labels_host[i]
+ * of the LAST i whose logits (n,Hv,Wv) exceed thr at its nearest source pixel (floor((i + 0.5) * in / out) in double, clamped) and keeps its
+ * value when none does.  labels_host: n HOST ints in 0..65535 (they travel as kernel arguments, 64 per launch; a longer list goes in
+ * successive launches in ascending order).  any_flag (optional, device int) is OR-ed with 1 when a pixel was written.  n = 0 paints nothing. */
+int saber_k_paint_nearest_stack(const float* logits, int n, int Hv, int Wv, const int* labels_host, float thr, uint16_t* plane, int H, int W,
+                                int* any_flag, void* stream);
+/* vol (Z,HW) uint16 in place: vol[z][i] = lut[z * L + vol[z][i]] where vol[z][i] < L, larger values pass through.  lut: (Z,L) uint16 on the
+ * device, L >= 1.  HW may be odd (frames then start off the 16-byte boundary).  The presence filter of SAM2Adapter.segment_volume
+ * (saber/adapters/sam2/predictor.py:340-346) is this call with an identity-or-zero table. */
+int saber_k_relabel_frames(uint16_t* vol, int Z, int64_t HW, const uint16_t* lut, int L, void* stream);
+/* acc[i] = max(acc[i], binarize ? (src[i] > 0) : src[i]) for i < n: np.maximum(final, masks3d > 0) / np.maximum(final, masks3d) of
+ * saber/segmenters/propagation.py:97-99 and tomo.py:246 */
+int saber_k_merge_max_u16(uint16_t* acc, const uint16_t* src, int64_t n, int binarize, void* stream);
+/* for i < n with v = src[i], 0 < v < L and conf[v] > best[i] (strictly): final_labels[i] = cls[v], best[i] = conf[v].  cls (L) uint16 and conf (L)
+ * float32 on the device, indexed by the label in src; entry 0 is never applied.  The per-mask loop of propagationSegmenter.multiclass_segment
+ * (saber/segmenters/propagation.py:150-158) in one pass: every voxel of src carries one label. */
+int saber_k_merge_class_conf(uint16_t* final_labels, float* best, const uint16_t* src, const uint16_t* cls, const float* conf, int L, int64_t n,
+                             void* stream);
 /* out (n,H,W) bytes, 1 where bit (x & 31) of bits[n][y][x >> 5] is set: the bool `segmentation` arrays of SAM2AutomaticMaskGenerator's
  * dict list (saber/adapters/sam2/automask.py:50-56 hands them to the segmenters), unpacked before the copy to the host */
 int saber_k_unpack_masks(const uint32_t* bits, int n, int H, int W, uint8_t* out, void* stream);

@@ -124,11 +124,17 @@ class SAM2Adapter(BaseAdapter):
 
     @torch.inference_mode()
     def segment_volume(self, start_frame_idx: int, masks=None, vol_shape=None, max_frame_num_to_track=None,
-                       min_presence_score: float = 0.5, inference_state=None) -> np.ndarray:
+                       min_presence_score: float = 0.5, inference_state=None, *, device_volume: bool = False):
         """Bidirectional propagation + presence-score filter, predictor.py:232-348 step by step.  The reference captures the mask decoder's
         object-score logits with a forward hook and files them under `_current_frame`, which it updates only AFTER the generator has
-        yielded a frame: a frame's scores therefore land on the frame yielded before it.  Reproduced as is (it feeds the boundary fit)."""
+        yielded a frame: a frame's scores therefore land on the frame yielded before it.  Reproduced as is (it feeds the boundary fit).
+        device_volume=True: the same label volume stays on the device (saber_amd/utils/labelvol.py, csrc/labelvol.hip) - one paint launch
+        per frame for all its objects, the presence filter as one (Z, n + 1) table look-up - and comes back as the (Z,H,W) int16 tensor
+        of uint16 values Engine.separate_masks accepts; frame_metrics and frame_scores are filled as on the host route."""
         from saber_amd.filters.estimate_thickness import fit_organelle_boundaries
+        if device_volume:
+            from saber_amd.utils import labelvol, volprep
+            labelvol.require_device(self.device, "SAM2Adapter.segment_volume(device_volume=True)")
         state = inference_state or self.inference_state
         if state is None:
             raise RuntimeError("Call set_volume() before segment_volume().")
@@ -164,6 +170,12 @@ class SAM2Adapter(BaseAdapter):
                         raise RuntimeError(state.lib.saber_k_last_error().decode())
                 painted.add(frame_idx)
 
+            def _apply_stack(frame_idx, obj_ids, mask_logits, want_flag=False):
+                labelvol.paint_nearest_stack(mask_logits, obj_ids, vol_dev[frame_idx], 0.0, flag if want_flag else None)
+                painted.add(frame_idx)
+
+            if device_volume:
+                _apply = _apply_stack
             for frame_idx, obj_ids, mask_logits, _, _ in self.propagate_in_video(start_frame_idx, max_frame_num_to_track, False, state):
                 current["frame"] = frame_idx
                 _apply(frame_idx, obj_ids, mask_logits, want_flag=(frame_idx == start_frame_idx))
@@ -173,7 +185,7 @@ class SAM2Adapter(BaseAdapter):
                 # forward masks painted a pixel is the one thing read back here
                 if frame_idx not in painted or (frame_idx == start_frame_idx and int(flag.item()) == 0):
                     _apply(frame_idx, obj_ids, mask_logits)
-            vol_masks = vol_dev.cpu().numpy().view(np.uint16)
+            vol_masks = None if device_volume else vol_dev.cpu().numpy().view(np.uint16)
         finally:
             state.hook = None
         n_masks = len(mask_list)
@@ -187,14 +199,18 @@ class SAM2Adapter(BaseAdapter):
                 frame_scores[fidx, :n] = v[:n]
             self.frame_scores = frame_scores
             bounds = fit_organelle_boundaries(frame_scores, plot=False)
+            if device_volume:          # the filter below as one table, uploaded once: nothing of volume size crosses to the host
+                labelvol.relabel_frames_(vol_dev, volprep.to_device_volume(labelvol.presence_keep_table(bounds, min_presence_score), vol_dev.device))
             for fidx in range(Z):
                 self.frame_metrics[fidx] = {}
                 for mi in range(n_masks):
                     obj_id = mi + 1
                     ps = float(bounds[fidx, mi])
                     self.frame_metrics[fidx][obj_id] = {"presence_score": ps}
-                    if ps < min_presence_score:
+                    if ps < min_presence_score and not device_volume:
                         vol_masks[fidx][vol_masks[fidx] == obj_id] = 0
+        if device_volume:
+            return vol_dev
         return vol_masks.astype(np.uint16)
 
     def clear_all_prompts_in_frame(self, *args, inference_state=None, **kwargs):

@@ -315,6 +315,21 @@ extern "C" int saber_k_normalize_minmax(float* v, int64_t n, const float* minmax
 extern "C" int saber_k_project_mean(const float* vol, int Z, int H, int W, int z0, int z1, float* out, void* stream) {
     return kcheck(launch_project_mean(vol, Z, H, W, z0, z1, out, (hipStream_t)stream));
 }
+// propagated label volumes (labelvol.hip)
+extern "C" int saber_k_paint_nearest_stack(const float* logits, int n, int Hv, int Wv, const int* labels_host, float thr, uint16_t* plane, int H, int W,
+                                           int* any_flag, void* stream) {
+    return kcheck(launch_paint_nearest_stack(logits, n, Hv, Wv, labels_host, thr, plane, H, W, any_flag, (hipStream_t)stream));
+}
+extern "C" int saber_k_relabel_frames(uint16_t* vol, int Z, int64_t HW, const uint16_t* lut, int L, void* stream) {
+    return kcheck(launch_relabel_frames(vol, Z, HW, lut, L, (hipStream_t)stream));
+}
+extern "C" int saber_k_merge_max_u16(uint16_t* acc, const uint16_t* src, int64_t n, int binarize, void* stream) {
+    return kcheck(launch_merge_max_u16(acc, src, n, binarize, (hipStream_t)stream));
+}
+extern "C" int saber_k_merge_class_conf(uint16_t* final_labels, float* best, const uint16_t* src, const uint16_t* cls, const float* conf, int L, int64_t n,
+                                        void* stream) {
+    return kcheck(launch_merge_class_conf(final_labels, best, src, cls, conf, L, n, (hipStream_t)stream));
+}
 extern "C" int saber_k_add_to_bf16(const float* x, const float* y, int y_rows, uint16_t* out_bf16, float* out_f32, int64_t rows, int C, void* stream) {
     return kcheck(launch_add_to_bf16(x, y, y_rows, out_bf16, out_f32, rows, C, (hipStream_t)stream));
 }

@@ -94,6 +94,13 @@ const char* launch_correlate1d_zero(const void* in, int dtype, float* out, int64
                                     int chunk_len, float* minmax, hipStream_t s);
 const char* launch_normalize_minmax(float* v, int64_t n, const float* minmax, hipStream_t s);
 const char* launch_project_mean(const float* vol, int Z, int H, int W, int z0, int z1, float* out, hipStream_t s);
+// ------------------------------------------------------------------ labelvol.hip: propagated label volumes (stacked paint, per-frame relabel, merges)
+// labels: n host ints (0..65535), object i paints labels[i]; the result equals n launch_paint_nearest calls in list order
+const char* launch_paint_nearest_stack(const float* logits, int n, int Hv, int Wv, const int* labels, float thr, uint16_t* plane, int H, int W,
+                                       int* any_flag, hipStream_t s);
+const char* launch_relabel_frames(uint16_t* vol, int Z, int64_t HW, const uint16_t* lut, int L, hipStream_t s);
+const char* launch_merge_max_u16(uint16_t* acc, const uint16_t* src, int64_t n, int binarize, hipStream_t s);
+const char* launch_merge_class_conf(uint16_t* fin, float* best, const uint16_t* src, const uint16_t* cls, const float* conf, int L, int64_t n, hipStream_t s);
 const char* launch_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res,
                                     hipStream_t s);
 const char* launch_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images,

@@ -123,11 +123,20 @@ class saber3D(saber2D):
         self.confidence_debug = False
         self.nframes = None
         self.filter_threshold = 0.5
+        self.device_volumes = False         # True: propagated label volumes stay on self.device (utils/labelvol.py, csrc/labelvol.hip); the segmenters' merges run there
 
     def propagate(self, mask_shape, target_class: Optional[int] = 1):
-        """Seed masks into the adapter and propagate bidirectionally (reference :265-280)."""
+        """Seed masks into the adapter and propagate bidirectionally (reference :265-280).  With device_volumes the volume comes back
+        as the adapter's device tensor (SAM2Adapter.segment_volume(device_volume=True)) instead of a numpy array."""
         arrays = [m["segmentation"] for m in self.masks] if isinstance(self.masks[0], dict) else self.masks
+        route = {"device_volume": True} if self.device_volumes else {}
         vol = self.video_predictor.segment_volume(start_frame_idx=self.ann_frame_idx, masks=arrays, vol_shape=mask_shape,
-                                                  max_frame_num_to_track=self.nframes, min_presence_score=self.filter_threshold)
+                                                  max_frame_num_to_track=self.nframes, min_presence_score=self.filter_threshold, **route)
         self.video_predictor.reset_state()
         return vol
+
+    def _stitch_device(self, acc: torch.Tensor) -> np.ndarray:
+        """utils.separate_masks of a device accumulator: 3-D components on the device (Engine.separate_masks, the host call's default
+        min_mask_area), one download, the host route's uint32 array"""
+        labels, _ = self.adapter.engine.separate_masks(acc, 100)
+        return labels.cpu().numpy().view(np.uint32)

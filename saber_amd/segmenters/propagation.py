@@ -46,6 +46,8 @@ class propagationSegmenter(saber3D):
 
     @torch.inference_mode()
     def single_segment(self, volume: np.ndarray, text_prompt: str = None):
+        if self.device_volumes:
+            return self._single_segment_device(volume, text_prompt)
         final = np.zeros(volume.shape, dtype=np.uint16)
         for ii in range(2, volume.shape[0], self.ini_depth):
             masks = self.segment_image(volume[ii], display=False, target_class=self.target_class, text_prompt=text_prompt)
@@ -57,14 +59,34 @@ class propagationSegmenter(saber3D):
             np.maximum(final, masks3d, out=final)
         return utils.separate_masks(final)
 
+    def _single_segment_device(self, volume, text_prompt):
+        """single_segment with the union kept on the device: merge_max_u16 per seed slice (binarised exactly where the host loop
+        binarises), the 3-D stitch on the device, one download"""
+        from saber_amd.utils import labelvol
+        dev = labelvol.require_device(self.device, "propagationSegmenter with device_volumes")
+        final = torch.zeros(tuple(volume.shape), dtype=torch.int16, device=dev)
+        for ii in range(2, volume.shape[0], self.ini_depth):
+            masks = self.segment_image(volume[ii], display=False, target_class=self.target_class, text_prompt=text_prompt)
+            if len(masks) == 0:
+                continue
+            masks3d = self.segment_3d(volume, [m["segmentation"] for m in masks], ann_frame_idx=ii)
+            labelvol.merge_max_u16_(final, masks3d, binarize=self.target_class > 0)
+        return self._stitch_device(final)
+
     @torch.inference_mode()
     def multiclass_segment(self, volume: np.ndarray):
         """propagation.py:119-160: per seed slice the raw 2-D masks are classified, the non-background ones propagated, and every voxel keeps
         the class of the most confident mask that reached it.  (The reference prepares the slice and hands the prepared RGB image to
         segment_image_2d, which prepares it again; kept.)"""
         from saber_amd.utils import preprocessing
-        final = np.zeros(volume.shape, dtype=np.uint16)
-        best = np.zeros(volume.shape, dtype=np.float32)
+        if self.device_volumes:
+            from saber_amd.utils import labelvol, volprep
+            dev = labelvol.require_device(self.device, "propagationSegmenter with device_volumes")
+            final_dev = torch.zeros(tuple(volume.shape), dtype=torch.int16, device=dev)
+            best_dev = torch.zeros(tuple(volume.shape), dtype=torch.float32, device=dev)
+        else:
+            final = np.zeros(volume.shape, dtype=np.uint16)
+            best = np.zeros(volume.shape, dtype=np.float32)
         for ii in range(2, volume.shape[0], self.ini_depth):
             im = preprocessing.prepare(volume[ii], to_rgb=True)
             im = im.cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
@@ -79,6 +101,13 @@ class propagationSegmenter(saber3D):
             if not np.any(valid):
                 continue
             masks3d = self.segment_3d(volume, [raw[i]["segmentation"] for i, v in enumerate(valid) if v], ann_frame_idx=ii)
+            if self.device_volumes:
+                # the loop below as one pass: tables indexed by object id (idx + 1), entry 0 = background, never applied
+                cids = classes[valid]
+                cls = np.concatenate([[0], cids]).astype(np.uint16)
+                conf = np.concatenate([[0], predictions[valid][np.arange(len(cids)), cids]]).astype(np.float32)
+                labelvol.merge_class_conf_(final_dev, best_dev, masks3d, volprep.to_device_volume(cls, dev), torch.from_numpy(conf).to(dev))
+                continue
             for idx, (probs, cid) in enumerate(zip(predictions[valid], classes[valid])):
                 region = masks3d == (idx + 1)
                 if np.any(region):
@@ -86,6 +115,8 @@ class propagationSegmenter(saber3D):
                     upd = region & (conf > best)
                     final[upd] = cid
                     best[upd] = conf
+        if self.device_volumes:
+            return final_dev.cpu().numpy().view(np.uint16)
         return final
 
     @torch.inference_mode()

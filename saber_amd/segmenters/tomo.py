@@ -100,7 +100,11 @@ class multiDepthTomoSegmenter(tomoSegmenter):
     def single_segment(self, vol, thickness, num_slabs, delta_z):
         from saber_amd.segmenters import utils
         depth = vol.shape[0]
-        combined = np.zeros(vol.shape, dtype=np.uint16)
+        if self.device_volumes:          # the union stays on the device (csrc/labelvol.hip), so does the stitch; one download
+            from saber_amd.utils import labelvol
+            combined = torch.zeros(tuple(vol.shape), dtype=torch.int16, device=labelvol.require_device(self.device, "multiDepthTomoSegmenter with device_volumes"))
+        else:
+            combined = np.zeros(vol.shape, dtype=np.uint16)
         for i in range(num_slabs):
             centre = int(depth // 2 + (i - num_slabs // 2) * delta_z)
             if centre < 0 or centre >= depth:
@@ -109,5 +113,8 @@ class multiDepthTomoSegmenter(tomoSegmenter):
             masks3d = self.segment_vol(vol, thickness, zSlice=centre, display=False)
             if masks3d is None:
                 continue
-            np.maximum(combined, (masks3d > 0).astype(np.uint16), out=combined)
-        return utils.separate_masks(combined)
+            if self.device_volumes:
+                labelvol.merge_max_u16_(combined, masks3d, binarize=True)
+            else:
+                np.maximum(combined, (masks3d > 0).astype(np.uint16), out=combined)
+        return self._stitch_device(combined) if self.device_volumes else utils.separate_masks(combined)
