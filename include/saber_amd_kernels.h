@@ -36,6 +36,15 @@ int saber_k_gemm_rowln(const uint16_t* A, int lda, const uint16_t* W, int ldw, c
                        uint16_t* out_bf16, const float* ln_gamma, const float* ln_beta, float ln_eps, uint16_t* ln_out, int M, int N, int K,
                        void* stream);
 
+/* The MLP of a Hiera block + residual + the LayerNorm that follows, in one kernel that keeps the hidden activation on chip:
+ * h = bf16(GELU(A[M,C] . W1[4C,C]^T + b1));  y = h . W2[C,4C]^T + b2 + res -> out_f32 (and out_bf16 = bf16(y) if not NULL);
+ * ln_out = bf16(LayerNorm(y) * ln_gamma + ln_beta).  Same roundings as saber_k_gemm_ld (GELU, bf16 out) followed by saber_k_gemm_rowln.
+ * C must be 144; W1 / W2 rows zero-padded to a multiple of 64 in K (ldw1 >= 192, ldw2 >= 576); res may alias out_f32 and ln_out may alias A
+ * (a row is read before it is written, by the wave that owns it). */
+int saber_k_mlp_rowln(const uint16_t* A, int lda, const uint16_t* W1, int ldw1, const float* b1, const uint16_t* W2, int ldw2, const float* b2,
+                      const float* res, float* out_f32, uint16_t* out_bf16, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                      uint16_t* ln_out, int M, int C, void* stream);
+
 /* nn.LayerNorm over the last dim; fp32 in, fp32 and/or bf16 out. */
 int saber_k_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* out_f32, uint16_t* out_bf16,
                       int rows, int C, int act, void* stream);

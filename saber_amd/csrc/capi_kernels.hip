@@ -27,6 +27,7 @@ extern "C" int saber_k_init(int device_id) {
     if (hipSetDevice(device_id) != hipSuccess) return kfail("hipSetDevice failed");
     const char* m = gemm_init_device();
     if (!m) m = gemm_rowln_init_device();
+    if (!m) m = gemm_mlp_rowln_init_device();
     if (!m) m = hiera_attention_init_device();
     if (!m) m = image_ops_init_device();
     if (!m) m = decoder_fused_init_device();
@@ -85,6 +86,26 @@ extern "C" int saber_k_gemm_rowln(const uint16_t* A, int lda, const uint16_t* W,
     p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.w_kpad = 1; p.bias = bias; p.res = res; p.ldres = N; p.Cf = out_f32; p.ldcf = N; p.Cb = out_bf16; p.ldcb = N;
     p.M = M; p.N = N; p.K = K; p.ln_gamma = ln_gamma; p.ln_beta = ln_beta; p.ln_eps = ln_eps; p.ln_out = ln_out; p.ldln = N; p.Wpk = scratch;
     return kcheck(launch_gemm_rowln(p, (hipStream_t)stream));
+}
+
+extern "C" int saber_k_mlp_rowln(const uint16_t* A, int lda, const uint16_t* W1, int ldw1, const float* b1, const uint16_t* W2, int ldw2, const float* b2,
+                                 const float* res, float* out_f32, uint16_t* out_bf16, const float* ln_gamma, const float* ln_beta, float ln_eps, uint16_t* ln_out,
+                                 int M, int C, void* stream) {
+    // the kernel reads both weights as one fragment stream (the engine packs it once at finalize); here: into a scratch kept per thread
+    if (!gemm_mlp_rowln_width(C)) return kfail("mlp_rowln: width not built (C must be 144)");
+    static thread_local bf16_t* scratch = nullptr;
+    static thread_local size_t scratch_elems = 0;
+    const size_t need = gemm_mlp_rowln_packed_elems(C);
+    if (need > scratch_elems) {
+        if (scratch) { (void)hipDeviceSynchronize(); (void)hipFree(scratch); scratch = nullptr; scratch_elems = 0; }
+        if (hipMalloc(reinterpret_cast<void**>(&scratch), need * sizeof(bf16_t)) != hipSuccess) return kfail("mlp_rowln: scratch allocation failed");
+        scratch_elems = need;
+    }
+    if (const char* m = launch_pack_mlp_chunks(W1, ldw1, W2, ldw2, C, scratch, (hipStream_t)stream)) return kfail(m);
+    GemmParams p;
+    p.A = A; p.lda = lda; p.bias1 = b1; p.bias = b2; p.res = res; p.ldres = C; p.Cf = out_f32; p.ldcf = C; p.Cb = out_bf16; p.ldcb = C;
+    p.M = M; p.N = C; p.K = C; p.ln_gamma = ln_gamma; p.ln_beta = ln_beta; p.ln_eps = ln_eps; p.ln_out = ln_out; p.ldln = C; p.Wpk = scratch;
+    return kcheck(launch_gemm_mlp_rowln(p, (hipStream_t)stream));
 }
 
 extern "C" int saber_k_layernorm(const float* x, const float* gamma, const float* beta, float eps, float* out_f32, uint16_t* out_bf16,

@@ -18,7 +18,7 @@ struct LinW { const bf16_t* w = nullptr; const float* b = nullptr; int out = 0, 
               const uint8_t* w8 = nullptr; const uint8_t* sw8 = nullptr; int kp8 = 0, sw_rows = 0; };   // w8 / sw8: MXFP8 copy (e4m3 [out][kp8] + e8m0 [kp8 / 128][sw_rows][4], gemm_fp8.hip), weight format SABER_WEIGHTS_MXFP8 only   // wf: dense fp32 [out][in] copy, kept only when the exact-precision mode was requested before finalize (exact.hip)   // wpk: K-step-packed copy (gemm_rowln.hip)  // rows zero-padded to ldw = ceil(in/64)*64
 struct LnW { const float* g = nullptr; const float* b = nullptr; };
 
-struct BlockW { LnW n1, n2; LinW qkv, proj, fc1, fc2, sc; };
+struct BlockW { LnW n1, n2; LinW qkv, proj, fc1, fc2, sc; const bf16_t* mlp_pk = nullptr; };   // mlp_pk: fc1 + fc2 packed for the fused MLP kernel (gemm_mlp_rowln.hip: launch_pack_mlp_chunks), widths it is built for only
 
 struct AttnW { LinW q, k, v, o; const bf16_t* pe_proj = nullptr; const bf16_t* img_wT = nullptr; };  // img_wT: the image-side projection weight transposed, bf16 [256][128] (k_proj of tokens->image, q_proj of image->tokens): operand of the folds in decoder_tokens.hip  // pe_proj: dense PE projected by the image-side weight (k: tokens->image, q: image->tokens), bf16 [4096][128]
 struct DecLayerW { AttnW self_attn, t2i, i2t; LnW n1, n2, n3, n4; LinW mlp1, mlp2; };

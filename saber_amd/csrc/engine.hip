@@ -208,6 +208,7 @@ extern "C" int saber_engine_create(int device_id, const char* trunk, int max_ima
     {
         const char* m = gemm_init_device();
             if (!m) m = gemm_rowln_init_device();
+            if (!m) m = gemm_mlp_rowln_init_device();
         if (!m) m = amg_device_init();
         if (!m) m = hiera_attention_init_device();
         if (!m) m = image_ops_init_device();
@@ -567,6 +568,14 @@ extern "C" int saber_engine_finalize(saber_engine* e) {
                 if (const char* m = launch_pack_w_kstep(l->w, l->ldw, l->out, l->in, d, nullptr)) return eng_fail(e, SABER_ERR_INVALID, m);
                 l->wpk = d;
             }
+        }
+        // widths the fused MLP kernel is built for (stage 0 of Hiera-L): both MLP weights as the fragment stream it reads.  A field of the
+        // block, not of the LinWs: mk_gemm forwards LinW::wpk to every GEMM kernel, and this layout is no K-step-packed copy.
+        if (!e->padded && gemm_mlp_rowln_width(bs.dout) && i + 1 < e->blocks.size() && w.fc1.w && w.fc2.w && !w.fc1.w8 && !w.fc2.w8) {
+            bf16_t* d = nullptr;
+            TRY(eng_alloc(e, &d, gemm_mlp_rowln_packed_elems(bs.dout)));
+            if (const char* m = launch_pack_mlp_chunks(w.fc1.w, w.fc1.ldw, w.fc2.w, w.fc2.ldw, bs.dout, d, nullptr)) return eng_fail(e, SABER_ERR_INVALID, m);
+            w.mlp_pk = d;
         }
     }
     // ---- neck (+ conv_s0 / conv_s1 composed with their lateral convs; no_mem_embed folded into the 64^2 bias)
@@ -978,6 +987,10 @@ int eng_encode(saber_engine* e, const float* img_dev, int H, int W, int channels
     // Hiera-L); the padded-window trunks keep the separate pass (their norm1 also zeroes the window-padding rows).
     static const bool no_rowln = getenv("SABER_AMD_NO_ROWLN") != nullptr;      // development A/B switch
     const bool fuse = !e->padded && !no_rowln;
+    // mlp.layers.0 + GELU + mlp.layers.1 + residual + the next block's norm1 as one kernel that keeps the hidden activation on chip
+    // (gemm_mlp_rowln.hip: stage 0).  Development switch / flag 262144 restore the pair of launches.
+    static const bool no_mlpfuse = getenv("SABER_AMD_NO_MLPFUSE") != nullptr;
+    const bool mlpfuse = fuse && !no_mlpfuse && !(g_saber_debug_flags & 262144);
     const size_t nblocks = e->blocks.size();
     // window-padding rows (padded layout): the reference pads the normalised tokens with zeros before qkv
     ENG_KP(e, PC_LAYERNORM, 0.0, 0.0, ln_run(x, e->bw[0].n1, 1e-6f, n * tokens, e->blocks[0].din, nullptr, e->xn, ACT_NONE, s, nullptr, nullptr, 0, e->valid[0], tokens));
@@ -1034,6 +1047,19 @@ int eng_encode(saber_engine* e, const float* img_dev, int H, int W, int channels
             }
         }
         if (bs.din != bs.dout) { std::swap(x, xalt); tokens /= 4; ++stage; }
+        const bool has_next = i + 1 < nblocks;
+        if (mlpfuse && has_next && w.mlp_pk) {
+            GemmParams g = mk_gemm(e->xn, bs.dout, Nq, w.fc2);
+            g.K = bs.dout; g.W = nullptr; g.ldw = 0; g.w_kpad = 0; g.Wpk = w.mlp_pk; g.bias1 = w.fc1.b;
+            g.Cf = x; g.ldcf = bs.dout; g.res = x; g.ldres = bs.dout;
+            g.rev = 0;                   // forward, against the proj launch that wrote xn and x; the next qkv launch walks back over xn
+            if ((int)i == e->stage_ends[stage]) { g.Cb = e->sb[stage]; g.ldcb = bs.dout; }
+            g.ln_gamma = e->bw[i + 1].n1.g; g.ln_beta = e->bw[i + 1].n1.b; g.ln_eps = 1e-6f; g.ln_out = e->xn; g.ldln = bs.dout;
+            // both products' FLOPs; bytes of the fused form: xn and the weights read once, the residual read, y, its LayerNorm (and the stage copy) written
+            const double M = g.M, C = bs.dout;
+            ENG_KP(e, PC_GEMM, 2.0 * 2.0 * M * C * 4.0 * C, M * C * (2 + 4 + 4 + 2 + (g.Cb ? 2 : 0)) + 2.0 * 8.0 * C * C, launch_gemm_mlp_rowln(g, s));
+            continue;
+        }
         if (w.fc1.w8) {      // hidden activations leave the epilogue as the MX operand of mlp.layers.1
             GemmMxParams g = mk_gemm_mx(e, xn8, e->xn8_s, Nq, w.fc1);
             g.C8 = hid8; g.ldc8 = 4 * bs.dout; g.SC = e->hid8_s; g.sc_rows = e->mx_rows; g.act = ACT_GELU;
@@ -1044,7 +1070,6 @@ int eng_encode(saber_engine* e, const float* img_dev, int H, int W, int channels
             ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K * g.batch, gemm_bytes(g), launch_gemm(g, s));
         }
         const bool to_padded = e->padded && bs.din != bs.dout && stage == 2;
-        const bool has_next = i + 1 < nblocks;
         if (w.fc2.w8) {
             GemmMxParams g = mk_gemm_mx(e, hid8, e->hid8_s, Nq, w.fc2);
             g.Cf = x; g.ldcf = bs.dout; g.res = x; g.ldres = bs.dout;

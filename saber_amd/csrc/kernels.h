@@ -49,6 +49,7 @@ struct GemmParams {
     const float* ln_gamma = nullptr; const float* ln_beta = nullptr; float ln_eps = 1e-6f;
     bf16_t* ln_out = nullptr; int64_t ldln = 0;
     const bf16_t* Wpk = nullptr;     // W packed per K-step for the row-owner kernel (launch_pack_w_kstep)
+    const float* bias1 = nullptr;    // fused MLP (gemm_mlp_rowln.hip): bias of mlp.layers.0 (bias = that of mlp.layers.1, Wpk = launch_pack_mlp_chunks)
 };
 
 // ------------------------------------------------------------------ gemm_fp8.hip
@@ -194,9 +195,10 @@ namespace op_f16 {
 // one-time kernel attribute setup: both builds
 #define SABER_OP_INIT(fn)                                                                                                 \
     inline const char* fn() { const char* m = op_bf16::fn(); return m ? m : op_f16::fn(); }
-SABER_OP_INIT(gemm_init_device) SABER_OP_INIT(gemm_rowln_init_device) SABER_OP_INIT(hiera_attention_init_device)
+SABER_OP_INIT(gemm_init_device) SABER_OP_INIT(gemm_rowln_init_device) SABER_OP_INIT(gemm_mlp_rowln_init_device) SABER_OP_INIT(hiera_attention_init_device)
 SABER_OP_INIT(decoder_fused_init_device) SABER_OP_INIT(decoder_tokens_init_device) SABER_OP_INIT(decoder_t16_init_device)
 SABER_OP_FWD(launch_gemm) SABER_OP_FWD(gemm_rowln_supported) SABER_OP_FWD(launch_gemm_rowln) SABER_OP_FWD(gemm_rowln_packed_elems) SABER_OP_FWD(launch_pack_w_kstep)
+SABER_OP_FWD(gemm_mlp_rowln_width) SABER_OP_FWD(gemm_mlp_rowln_packed_elems) SABER_OP_FWD(launch_pack_mlp_chunks) SABER_OP_FWD(launch_gemm_mlp_rowln)
 SABER_OP_FWD(launch_layernorm) SABER_OP_FWD(launch_gather_rows) SABER_OP_FWD(launch_add_to_bf16) SABER_OP_FWD(launch_hiera_attention)
 SABER_OP_FWD(launch_prompt_tokens) SABER_OP_FWD(launch_prompt_tokens_multi) SABER_OP_FWD(launch_mask_embed_src) SABER_OP_FWD(launch_mask_hidden) SABER_OP_FWD(launch_embb_tiles)
 SABER_OP_FWD(launch_dec_attention) SABER_OP_FWD(launch_mask_pick) SABER_OP_FWD(launch_iou_live_flags) SABER_OP_FWD(launch_mask_select)

@@ -10,6 +10,13 @@ const char* gemm_rowln_init_device();
 // W [N][ldw] (rows zero-padded) -> Wpk[ceil(K/32)][N][32] with the LDS chunk permutation of the row-owner kernel applied
 size_t gemm_rowln_packed_elems(int N, int K);
 const char* launch_pack_w_kstep(const bf16_t* W, int ldw, int N, int K, bf16_t* out, hipStream_t s);
+// mlp.layers.0 + GELU + mlp.layers.1 + residual + the next LayerNorm in one kernel (gemm_mlp_rowln.hip), the hidden activation stays on chip:
+// p.A = xn [M][lda], p.N = p.K = C, p.Wpk = the launch_pack_mlp_chunks copy of both weights, p.bias1 / p.bias = b1 / b2, outputs as launch_gemm_rowln
+bool gemm_mlp_rowln_width(int C);                  // widths the kernel is built and enabled for
+size_t gemm_mlp_rowln_packed_elems(int C);
+const char* launch_pack_mlp_chunks(const bf16_t* W1, int ldw1, const bf16_t* W2, int ldw2, int C, bf16_t* out, hipStream_t s);
+const char* launch_gemm_mlp_rowln(const GemmParams& p, hipStream_t stream);
+const char* gemm_mlp_rowln_init_device();
 const char* launch_layernorm(const LayerNormParams& p, hipStream_t s);
 // out[img][r][:] = idx[r] >= 0 ? in[img][idx[r]][:] : 0   (re-ordering between the engine's token orders; fp32 rows of C floats)
 const char* launch_gather_rows(const float* in, int64_t in_rows, float* out, int64_t out_rows, const int* idx, int C, int n_images, hipStream_t s);
