@@ -165,6 +165,31 @@ int saber_k_bf16_to_f32(const uint16_t* x, int64_t n, float* out, void* stream);
 int saber_k_gemm_batched(const uint16_t* A, int lda, int64_t strideA, const uint16_t* W, int ldw, int64_t strideW, const float* bias, float* out_f32,
                          int ldcf, int64_t strideCf, uint16_t* out_bf16, int ldcb, int64_t strideCb, int M, int N, int K, int batch, void* stream);
 
+/* ---- the memory attention of all tracked objects of a frame in one set of launches (VideoPredictor(batch_objects=True)).  Each entry gives
+ * every object of the batch the bits of the single-problem entry it stands for. */
+/* saber_k_flash256 for `batch` problems of one shape: object b reads Q + b * q_stride (0: the queries are shared), K + b * k_stride, V + b * v_stride
+ * and writes out + b * o_stride (strides in elements, multiples of 8).  The split over the keys is the one saber_k_flash256 picks for ONE problem
+ * of n_q / n_keys; ws: batch * (n_q / 64) * split * 64 * 258 floats (NULL: no split, as saber_k_flash256; non-NULL but too small: an error) */
+int saber_k_flash256_batched(const uint16_t* Q, int64_t q_stride, const uint16_t* K, int64_t k_stride, const uint16_t* V, int64_t v_stride, int n_q, int n_keys,
+                             int batch, float scale, const float* bias_v, uint16_t* out, int64_t o_stride, float* ws, int64_t ws_floats, void* stream);
+/* saber_k_rope on `batch` stacked blocks of rows_per rows: a row is rotated when row % rows_per < n_rot, with the token of row % rows_per
+ * (the keys of stacked memory banks: every bank's pointer-token rows are copied) */
+int saber_k_rope_batched(const float* x, int64_t rows_per, int batch, int n_rot, int C, int side, float theta, float* out_f32, uint16_t* out_bf16, void* stream);
+/* the memory banks of `batch` objects: mem_out[b] = [n_mem stored (4096, 64) 16-bit memories ..., n_ptr_rows pointer-token rows], kin_out[b] =
+ * 16-bit(float(mem) + position), both [batch][Nkp][64] with Nkp = (4096 n_mem + n_ptr_rows) rounded up to 64 and the rows beyond the bank zero.
+ * mem_ptrs / pos_idx: batch * n_mem HOST entries (object-major): device pointers of the memories (n_mem <= 7) and the index of each memory's
+ * position table in pos_tables [n_tables][4096][64] fp32; ptr_tok (16-bit) / ptr_pos (fp32): [n_ptr_rows][64] per object at the given element
+ * strides (0: shared by the batch), NULL with n_ptr_rows = 0.  What saber_k_bf16_to_f32 + saber_k_add_to_bf16 compute on a concatenated bank. */
+int saber_k_membank_assemble(const void* const* mem_ptrs, const int* pos_idx, int n_mem, const float* pos_tables, int n_tables, const uint16_t* ptr_tok,
+                             int64_t ptr_tok_stride, const float* ptr_pos, int64_t ptr_pos_stride, int n_ptr_rows, int batch, uint16_t* mem_out, uint16_t* kin_out,
+                             void* stream);
+/* saber_k_gemm_ld for `batch` problems that share W and bias: object b reads A + b * strideA (and res + b * strideRes; 0: a shared residual) and
+ * writes out_f32 + b * strideCf / out_bf16 + b * strideCb, leading dimensions N.  Every object keeps its own M, so it takes the kernel - and the
+ * summation order - of the single call.  Shapes for which saber_k_gemm_ld reads W packed per K-step are refused (that route has no batch). */
+int saber_k_gemm_ld_batched(const uint16_t* A, int lda, int64_t strideA, const uint16_t* W, int ldw, int w_kpad, const float* bias, const float* res,
+                            int64_t strideRes, float* out_f32, int64_t strideCf, uint16_t* out_bf16, int64_t strideCb, int M, int N, int K, int act, int batch,
+                            void* stream);
+
 /* engine token order helpers (DESIGN.md "token order") */
 /* Folded image->token attention of the two-way transformer (reference: sam2 TwoWayAttentionBlock.cross_attn_image_to_token +
  * norm4, called from sam2/modeling/sam/transformer.py via saber/adapters/sam2/automask.py's predictor):

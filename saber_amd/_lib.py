@@ -161,6 +161,10 @@ SIGNATURES = {
     "saber_k_add_to_bf16": (_i, [_vp, _vp, _i, _vp, _vp, C.c_int64, _i, _vp]),
     "saber_k_bf16_to_f32": (_i, [_vp, C.c_int64, _vp, _vp]),
     "saber_k_gemm_batched": (_i, [_vp, _i, C.c_int64, _vp, _i, C.c_int64, _vp, _vp, _i, C.c_int64, _vp, _i, C.c_int64, _i, _i, _i, _i, _vp]),
+    "saber_k_flash256_batched": (_i, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _i, _f, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "saber_k_rope_batched": (_i, [_vp, C.c_int64, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "saber_k_membank_assemble": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _vp, _vp, _vp]),
+    "saber_k_gemm_ld_batched": (_i, [_vp, _i, C.c_int64, _vp, _i, _i, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _i, _i, _i, _vp]),
     "saber_k_xg_gemm": (_i, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _i,
                              C.c_int64, C.c_int64, C.c_int64, _i, _i, _vp, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "saber_k_xg_layernorm": (_i, [_vp, _vp, _vp, _f, _vp, C.c_int64, _i, _i, _vp, _i, _vp]),

@@ -124,13 +124,16 @@ class SAM2Adapter(BaseAdapter):
 
     @torch.inference_mode()
     def segment_volume(self, start_frame_idx: int, masks=None, vol_shape=None, max_frame_num_to_track=None,
-                       min_presence_score: float = 0.5, inference_state=None, *, device_volume: bool = False):
+                       min_presence_score: float = 0.5, inference_state=None, *, device_volume: bool = False,
+                       batch_objects: Optional[bool] = None):
         """Bidirectional propagation + presence-score filter, predictor.py:232-348 step by step.  The reference captures the mask decoder's
         object-score logits with a forward hook and files them under `_current_frame`, which it updates only AFTER the generator has
         yielded a frame: a frame's scores therefore land on the frame yielded before it.  Reproduced as is (it feeds the boundary fit).
         device_volume=True: the same label volume stays on the device (saber_amd/utils/labelvol.py, csrc/labelvol.hip) - one paint launch
         per frame for all its objects, the presence filter as one (Z, n + 1) table look-up - and comes back as the (Z,H,W) int16 tensor
-        of uint16 values Engine.separate_masks accepts; frame_metrics and frame_scores are filled as on the host route."""
+        of uint16 values Engine.separate_masks accepts; frame_metrics and frame_scores are filled as on the host route.
+        batch_objects=True / False: the memory attention of all objects of a frame as one set of launches, or object by object, for this
+        call (VideoPredictor.batch_objects; same bits either way); None keeps the video predictor's own setting (SABER_AMD_VIDEO_BATCH)."""
         from saber_amd.filters.estimate_thickness import fit_organelle_boundaries
         if device_volume:
             from saber_amd.utils import labelvol, volprep
@@ -147,6 +150,9 @@ class SAM2Adapter(BaseAdapter):
         current = {"frame": None}
         captured: Dict[Any, list] = {}
         state.hook = lambda score: captured.setdefault(current["frame"], []).append(np.array([score], dtype=np.float32))
+        was_batched = state.batch_objects
+        if batch_objects is not None:
+            state.batch_objects = bool(batch_objects)
         try:
             for obj_id, mask in enumerate(mask_list, start=1):
                 if np.max(mask) == 0:
@@ -188,6 +194,7 @@ class SAM2Adapter(BaseAdapter):
             vol_masks = None if device_volume else vol_dev.cpu().numpy().view(np.uint16)
         finally:
             state.hook = None
+            state.batch_objects = was_batched
         n_masks = len(mask_list)
         if n_masks > 0:
             frame_scores = np.zeros([Z, n_masks])

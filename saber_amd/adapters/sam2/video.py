@@ -98,6 +98,39 @@ def window_shares(k: int, world: int) -> List[Tuple[int, int]]:
     return [(min(k, r * per), min(k, (r + 1) * per)) for r in range(world)]
 
 
+def bank_signature(st: dict, t: int, reverse: bool, num_maskmem: int, num_frames: int) -> Tuple[tuple, tuple]:
+    """What the memory bank of one object looks like on frame t, from its outputs st = {"cond": {frame: ...}, "non_cond": {frame: ...}}
+    alone (no device data): (temporal slot of every spatial memory, in bank order; offset of every object pointer, in bank order) - the
+    selection rules of VideoPredictor._memory_conditioned.  Objects with equal signatures have banks of one shape with the same position
+    rows, so their memory attention can run as one batch."""
+    slots = [num_maskmem - 1] * len(st["cond"])
+    for t_pos in range(1, num_maskmem):
+        t_rel = num_maskmem - t_pos
+        if (t + t_rel if reverse else t - t_rel) in st["non_cond"]:
+            slots.append(num_maskmem - t_pos - 1)
+    max_ptrs = min(num_frames, 16)
+    sign = -1 if reverse else 1
+    offs = [(t - tc) * sign for tc in st["cond"] if ((tc >= t) if reverse else (tc <= t))]
+    for d in range(1, max_ptrs):
+        tt = t + d if reverse else t - d
+        if tt < 0 or tt >= num_frames:
+            break
+        if tt in st["non_cond"]:
+            offs.append(d)
+    return tuple(slots), tuple(offs)
+
+
+def group_by_signature(oids: List[int], signatures: List[tuple], object_batch: int) -> List[List[int]]:
+    """Batches of the objects `oids` (parallel to `signatures`): objects of one signature form a group, in the order of `oids`; groups come in
+    the order of their first object; a group larger than object_batch is cut into chunks of at most object_batch."""
+    if object_batch < 1:
+        raise ValueError("object_batch must be at least 1")
+    groups: Dict[tuple, List[int]] = {}
+    for oid, sig in zip(oids, signatures):
+        groups.setdefault(sig, []).append(oid)
+    return [g[i:i + object_batch] for g in groups.values() for i in range(0, len(g), object_batch)]
+
+
 def load_tomogram_frames(tomogram: np.ndarray, image_size: int = 1024, light_modality: bool = False) -> np.ndarray:
     """TomogramPreprocessor as the adapter applies it (saber/adapters/preprocessing.py:27-76 via predictor.py:98-105): min-max to [-1,1],
     per-slice resize to image_size (skimage.transform.resize(anti_aliasing=True): the identity at image_size, order-1 interpolation at
@@ -166,9 +199,16 @@ def load_tomogram_frames_device(tomogram, lib, device, image_size: int = 1024, l
 class VideoPredictor:
     """add_new_mask / propagate_in_video of the SAM2 video predictor on one engine handle."""
 
-    def __init__(self, engine, weights: Dict[str, np.ndarray], num_maskmem: int = 2):
+    def __init__(self, engine, weights: Dict[str, np.ndarray], num_maskmem: int = 2, batch_objects: Optional[bool] = None, object_batch: int = 16):
+        """batch_objects: the memory attention of all objects that are tracked on a frame runs as one set of launches
+        (_memory_conditioned_batch; bit-identical to the per-object route); None = the environment switch SABER_AMD_VIDEO_BATCH=1, else off.
+        object_batch: most objects per batch (bounds the workspace and activations: ~0.1 GB per object)"""
         if num_maskmem > 7:
             raise ValueError("num_maskmem must be at most 7")
+        if object_batch < 1:
+            raise ValueError("object_batch must be at least 1")
+        self.batch_objects = os.environ.get("SABER_AMD_VIDEO_BATCH", "0") not in ("", "0") if batch_objects is None else bool(batch_objects)
+        self.object_batch = int(object_batch)
         self.eng, self.lib, self.dev = engine, engine.lib, engine.device
         # 16-bit operand type of the engine handle: every uint16 buffer of this class (GEMM weights, stored memories, attention operands)
         # holds that type's bit patterns
@@ -226,6 +266,8 @@ class VideoPredictor:
                      for i in range(2)}
         self._pe1d_cache: Dict[tuple, torch.Tensor] = {}
         self._flash_ws = None
+        self._flash_ws_batch = None
+        self._mem_pos_all = None         # mem_pos_t as one (num_maskmem, 4096, 64) table for saber_k_membank_assemble
         self.hook = None
         self.images = None
 
@@ -701,12 +743,158 @@ class VideoPredictor:
             x = self._lin(h, L + "linear2", 4096, res=x)
         return self._ln(x, "memory_attention.norm", 4096, 256, 1e-5, bf=False)
 
+    # ------------------------------------------------------------------ memory attention of all objects of a frame
+    def _gemm_b(self, A, strideA, key, B, M, out_bf=False, res=None, stride_res=0, act=ACT_NONE, bias=True, out=None, stride_out=None):
+        """saber_k_gemm_ld for B objects in one launch (the GEMM's batch dimension: every object keeps its own M, so the kernel and the
+        summation order are those of _lin / _gemm on one object).  out (optional): a buffer of B blocks of stride_out elements"""
+        w = self.bf[key + ".weight"]
+        N, K = w.shape
+        if out is None:
+            out, stride_out = self._new(B, M, N, dtype=torch.uint16 if out_bf else torch.float32), M * N
+        self._ck(self.lib.saber_k_gemm_ld_batched(self._p(A), K, strideA, self._p(w), K, 1 if K % 64 == 0 else 0, self._p(self.f32[key + ".bias"]) if bias else None,
+                                                  self._p(res), stride_res, None if out_bf else self._p(out), 0 if out_bf else stride_out,
+                                                  self._p(out) if out_bf else None, stride_out if out_bf else 0, M, N, K, act, B, self._s()))
+        return out
+
+    def _memory_conditioned_group(self, oids: List[int], t: int, reverse: bool, self0: dict) -> torch.Tensor:
+        """_memory_conditioned for objects of ONE bank signature: (len(oids), 4096, 256) fp32.  self0: layer 0 up to the cross attention's
+        queries, which does not depend on the object (_memory_conditioned_batch computes it once per frame)."""
+        B = len(oids)
+        slots, offs = bank_signature(self.out[oids[0]], t, reverse, self.num_maskmem, self.num_frames)
+        n_mem, n_ptr = len(slots), len(offs)
+        mems, ptrs = [], []
+        for oid in oids:                                   # the entries bank_signature counted, in its order
+            st = self.out[oid]
+            mems += [o["mem"] for o in st["cond"].values()]
+            for t_pos in range(1, self.num_maskmem):
+                t_rel = self.num_maskmem - t_pos
+                o = st["non_cond"].get(t + t_rel if reverse else t - t_rel)
+                if o is not None:
+                    mems.append(o["mem"])
+            cond_ptrs = [o["obj_ptr"] for tc, o in st["cond"].items() if ((tc >= t) if reverse else (tc <= t))]
+            ptrs += cond_ptrs + [st["non_cond"][t + d if reverse else t - d]["obj_ptr"] for d in offs[len(cond_ptrs):]]
+        assert len(mems) == B * n_mem and len(ptrs) == B * n_ptr
+        n_spatial, n_ptr_tok = 4096 * n_mem, 4 * n_ptr
+        Nk = n_spatial + n_ptr_tok
+        Nkp = (Nk + 63) // 64 * 64
+        max_ptrs = min(self.num_frames, 16)
+        tok = pe4 = None
+        if n_ptr:
+            # pointer tokens of all objects in one conversion; their position rows depend on the offsets alone: once per group
+            tok = self._to_bf(torch.cat(ptrs, 0).contiguous(), B * n_ptr, 256)                  # (B, 4 n_ptr, 64) 16-bit
+            key = (tuple(offs), max_ptrs)
+            pe_bf = self._pe1d_cache.get(key)
+            if pe_bf is None:
+                pe = _sine_pe_1d(np.asarray(offs, np.float32) / np.float32(max_ptrs - 1), 256)
+                pe_bf = self._to_bf(torch.from_numpy(pe).to(self.dev), n_ptr, 256)
+                if len(self._pe1d_cache) < 256:
+                    self._pe1d_cache[key] = pe_bf
+            pe4 = self._lin(pe_bf, "obj_ptr_tpos_proj", n_ptr).repeat_interleave(4, dim=0).contiguous()      # (4 n_ptr, 64) fp32
+        if self._mem_pos_all is None:
+            self._mem_pos_all = torch.stack(self.mem_pos_t, 0).contiguous()
+        mem_bf = self._new(B, Nkp, 64, dtype=torch.uint16)
+        kin_bf = self._new(B, Nkp, 64, dtype=torch.uint16)
+        mem_ptrs = (C.c_void_p * max(1, B * n_mem))(*[m.data_ptr() for m in mems])
+        pos_idx = (C.c_int * max(1, B * n_mem))(*(list(slots) * B))
+        self._ck(self.lib.saber_k_membank_assemble(mem_ptrs, pos_idx, n_mem, self._p(self._mem_pos_all), self.num_maskmem, self._p(tok), n_ptr_tok * 64,
+                                                   self._p(pe4), 0, n_ptr_tok, B, self._p(mem_bf), self._p(kin_bf), self._s()))
+        scale = 1.0 / 16.0
+        R = 4096 * 256
+
+        def attend(q_bf, q_stride, k_bf, k_stride, v_bf, v_stride, n_keys, bv):
+            O = self._new(B, 4096, 256, dtype=torch.uint16)
+            need = B * 64 * 8 * 64 * 258
+            if self._flash_ws_batch is None or self._flash_ws_batch.numel() < need:
+                self._flash_ws_batch = None
+                self._flash_ws_batch = self._new(need)
+            self._ck(self.lib.saber_k_flash256_batched(self._p(q_bf), q_stride, self._p(k_bf), k_stride, self._p(v_bf), v_stride, 4096, n_keys, B, scale,
+                                                       self._p(bv), self._p(O), R, self._p(self._flash_ws_batch), self._flash_ws_batch.numel(), self._s()))
+            return O
+
+        def rope(x_f32, rows_per, n_rot):
+            out = self._new(B, rows_per, 256, dtype=torch.uint16)
+            self._ck(self.lib.saber_k_rope_batched(self._p(x_f32), rows_per, B, n_rot, 256, 64, 10000.0, None, self._p(out), self._s()))
+            return out
+
+        x = None
+        for i in range(4):
+            L = f"memory_attention.layers.{i}."
+            if i == 0:
+                x_res, res_stride, q, q_stride = self0["x"], 0, self0["q"], 0
+            else:
+                tb = self._ln(x, L + "norm1", B * 4096, 256, 1e-5)
+                q = rope(self._gemm_b(tb, R, L + "self_attn.q_proj", B, 4096), 4096, 4096)
+                k = rope(self._gemm_b(tb, R, L + "self_attn.k_proj", B, 4096), 4096, 4096)
+                v = self._gemm_b(tb, R, L + "self_attn.v_proj", B, 4096, out_bf=True, bias=False)
+                O = attend(q, R, k, R, v, R, 4096, self.f32[L + "self_attn.v_proj.bias"])
+                x = self._gemm_b(O, R, L + "self_attn.out_proj", B, 4096, res=x, stride_res=R)
+                tb = self._ln(x, L + "norm2", B * 4096, 256, 1e-5)
+                q, q_stride = rope(self._gemm_b(tb, R, L + "cross_attn_image.q_proj", B, 4096), 4096, 4096), R
+                x_res, res_stride = x, R
+            kf = self._new(B, Nkp, 256, zero=True)
+            self._gemm_b(kin_bf, Nkp * 64, L + "cross_attn_image.k_proj", B, Nk, out=kf, stride_out=Nkp * 256)
+            k = rope(kf, Nkp, n_spatial)
+            v = self._new(B, Nkp, 256, dtype=torch.uint16)
+            self._gemm_b(mem_bf, Nkp * 64, L + "cross_attn_image.v_proj", B, Nk, out_bf=True, bias=False, out=v, stride_out=Nkp * 256)
+            O = attend(q, q_stride, k, Nkp * 256, v, Nkp * 256, Nk, self.f32[L + "cross_attn_image.v_proj.bias"])
+            x = self._gemm_b(O, R, L + "cross_attn_image.out_proj", B, 4096, res=x_res, stride_res=res_stride)
+            tb = self._ln(x, L + "norm3", B * 4096, 256, 1e-5)
+            h = self._gemm_b(tb, R, L + "linear1", B, 4096, out_bf=True, act=ACT_RELU)
+            x = self._gemm_b(h, 4096 * 2048, L + "linear2", B, 4096, res=x, stride_res=R)
+        return self._ln(x, "memory_attention.norm", B * 4096, 256, 1e-5, bf=False).view(B, 4096, 256)
+
+    def _memory_conditioned_batch(self, oids: List[int], t: int, raw: torch.Tensor, reverse: bool) -> torch.Tensor:
+        """_memory_conditioned of every object in `oids` on frame t: (len(oids), 4096, 256) fp32, row i = what _memory_conditioned(oids[i], ...)
+        returns, bit for bit.  Objects are grouped by bank signature (group_by_signature), a group is one batch of at most object_batch."""
+        if not oids:
+            return self._new(0, 4096, 256)
+        # layer 0 up to the queries of its cross attention reads raw + 0.1 curr_pos alone: once per frame, with the per-object route's calls
+        L = "memory_attention.layers.0."
+        x = self._new(4096, 256)
+        self._ck(self.lib.saber_k_axpy(self._p(raw), self._p(self.curr_pos), None, 0.1, 4096, 256, self._p(x), self._s()))
+
+        def rope1(x_f32):
+            out = self._new(4096, 256, dtype=torch.uint16)
+            self._ck(self.lib.saber_k_rope(self._p(x_f32), 4096, 4096, 256, 64, 10000.0, None, self._p(out), self._s()))
+            return out
+
+        tb = self._ln(x, L + "norm1", 4096, 256, 1e-5)
+        q = rope1(self._lin(tb, L + "self_attn.q_proj", 4096))
+        k = rope1(self._lin(tb, L + "self_attn.k_proj", 4096))
+        v = self._new(4096, 256, dtype=torch.uint16)
+        self._gemm(tb, self.bf[L + "self_attn.v_proj.weight"], None, 4096, 256, 256, out_bf=v)
+        O = self._new(4096, 256, dtype=torch.uint16)
+        if self._flash_ws is None:
+            self._flash_ws = self._new(64 * 8 * 64 * 258)
+        self._ck(self.lib.saber_k_flash256(self._p(q), self._p(k), self._p(v), 4096, 4096, 1.0 / 16.0, self._p(self.f32[L + "self_attn.v_proj.bias"]), self._p(O),
+                                           self._p(self._flash_ws), self._flash_ws.numel(), self._s()))
+        x = self._lin(O, L + "self_attn.out_proj", 4096, res=x)
+        tb = self._ln(x, L + "norm2", 4096, 256, 1e-5)
+        self0 = {"x": x, "q": rope1(self._lin(tb, L + "cross_attn_image.q_proj", 4096))}
+        sigs = [bank_signature(self.out[oid], t, reverse, self.num_maskmem, self.num_frames) for oid in oids]
+        out = self._new(len(oids), 4096, 256)
+        at = {oid: i for i, oid in enumerate(oids)}
+        for group in group_by_signature(oids, sigs, self.object_batch):
+            res = self._memory_conditioned_group(group, t, reverse, self0)
+            if len(group) == len(oids):
+                return res
+            out[[at[oid] for oid in group]] = res
+        return out
+
     # ------------------------------------------------------------------ tracking
     def _track(self, oid: int, t: int, reverse: bool) -> dict:
         raw = self._frame(t, reverse)
         cond = self._memory_conditioned(oid, t, raw, reverse)
         low, obj_v, ptr = self._sam_heads(cond, None, multimask=True, slot=self._slot(t))
         mfm = self._resize(low, 256, 256, 1024, 1024, antialias=0, post=1, a=20.0, c=-10.0)       # sigmoid(high-res logits) * 20 - 10
+        mem = self._encode_memory(raw, mfm, obj_v > 0)
+        return {"pred_masks": low, "obj_ptr": ptr, "obj": obj_v, "mem": mem}
+
+    def _track_from(self, cond: torch.Tensor, t: int, reverse: bool) -> dict:
+        """_track after the memory attention: cond = the object's memory-conditioned features (a row of _memory_conditioned_batch)"""
+        raw = self._frame(t, reverse)
+        low, obj_v, ptr = self._sam_heads(cond, None, multimask=True, slot=self._slot(t))
+        mfm = self._resize(low, 256, 256, 1024, 1024, antialias=0, post=1, a=20.0, c=-10.0)
         mem = self._encode_memory(raw, mfm, obj_v > 0)
         return {"pred_masks": low, "obj_ptr": ptr, "obj": obj_v, "mem": mem}
 
@@ -726,10 +914,22 @@ class VideoPredictor:
         Hv, Wv = self.video_hw
         for t in order:
             outs = []
+            conds = {}
+            if self.batch_objects:
+                # the memory attention of every object tracked on this frame in one set of launches; the SAM heads and the memory encoder
+                # below stay per object (an object's output reads its own memories alone, so the order of the two loops does not matter)
+                todo = [oid for oid in self.obj_ids if t not in self.out[oid]["cond"]]
+                if todo:
+                    raw = self._frame(t, reverse)
+                    conds = dict(zip(todo, self._memory_conditioned_batch(todo, t, raw, reverse)))
             for oid in self.obj_ids:
                 self._tracked[(oid, t)] = reverse
                 if t in self.out[oid]["cond"]:
                     low = self.out[oid]["cond"][t]["pred_masks"]
+                elif self.batch_objects:
+                    o = self._track_from(conds.pop(oid), t, reverse)
+                    self.out[oid]["non_cond"][t] = o
+                    low = o["pred_masks"]
                 else:
                     o = self._track(oid, t, reverse)
                     self.out[oid]["non_cond"][t] = o

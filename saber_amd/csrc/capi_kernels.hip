@@ -363,6 +363,36 @@ extern "C" int saber_k_gemm_batched(const uint16_t* A, int lda, int64_t strideA,
     return kcheck(launch_gemm(p, (hipStream_t)stream));
 }
 extern "C" int saber_k_bf16_to_f32(const uint16_t* x, int64_t n, float* out, void* stream) { return kcheck(launch_bf16_to_f32(x, n, out, (hipStream_t)stream)); }
+// ---- memory attention of all tracked objects of a frame (flash256.hip, video_ops.hip, gemm.hip's batch dimension)
+extern "C" int saber_k_flash256_batched(const uint16_t* Q, int64_t q_stride, const uint16_t* K, int64_t k_stride, const uint16_t* V, int64_t v_stride, int n_q, int n_keys,
+                                        int batch, float scale, const float* bias_v, uint16_t* out, int64_t o_stride, float* ws, int64_t ws_floats, void* stream) {
+    if (ws_floats < 0) return kfail("flash256_batched: ws_floats must be non-negative");
+    return kcheck(launch_flash256_batched(Q, q_stride, K, k_stride, V, v_stride, n_q, n_keys, batch, scale, bias_v, out, o_stride, ws, (size_t)ws_floats, (hipStream_t)stream));
+}
+extern "C" int saber_k_rope_batched(const float* x, int64_t rows_per, int batch, int n_rot, int C, int side, float theta, float* out_f32, uint16_t* out_bf16, void* stream) {
+    return kcheck(launch_rope_batched(x, rows_per, batch, n_rot, C, side, theta, out_f32, out_bf16, (hipStream_t)stream));
+}
+extern "C" int saber_k_membank_assemble(const void* const* mem_ptrs, const int* pos_idx, int n_mem, const float* pos_tables, int n_tables, const uint16_t* ptr_tok,
+                                        int64_t ptr_tok_stride, const float* ptr_pos, int64_t ptr_pos_stride, int n_ptr_rows, int batch, uint16_t* mem_out,
+                                        uint16_t* kin_out, void* stream) {
+    return kcheck(launch_membank_assemble(reinterpret_cast<const bf16_t* const*>(mem_ptrs), pos_idx, n_mem, pos_tables, n_tables, ptr_tok, ptr_tok_stride, ptr_pos,
+                                          ptr_pos_stride, n_ptr_rows, batch, mem_out, kin_out, (hipStream_t)stream));
+}
+extern "C" int saber_k_gemm_ld_batched(const uint16_t* A, int lda, int64_t strideA, const uint16_t* W, int ldw, int w_kpad, const float* bias, const float* res,
+                                       int64_t strideRes, float* out_f32, int64_t strideCf, uint16_t* out_bf16, int64_t strideCb, int M, int N, int K, int act, int batch,
+                                       void* stream) {
+    if (batch < 1 || batch > 65535) return kfail("gemm_ld_batched: batch must be in 1..65535");
+    if (strideA < 0 || strideRes < 0 || (batch > 1 && ((out_f32 && strideCf < (int64_t)M * N) || (out_bf16 && strideCb < (int64_t)M * N))))
+        return kfail("gemm_ld_batched: bad stride (outputs must not overlap)");
+    // saber_k_gemm_ld's packed-W route (persistent 256 x 256 tiles) has no batch dimension: its summation order cannot be reproduced here
+    if (w_kpad && out_bf16 && !out_f32 && !res && (K % 64) == 0 && (N & 7) == 0 && ((int64_t)M * N >= (int64_t)1024 * 65536 || (g_saber_debug_flags & 128)))
+        return kfail("gemm_ld_batched: this shape takes saber_k_gemm_ld's packed-W route, which has no batch dimension");
+    GemmParams p;
+    p.A = A; p.lda = lda; p.strideA = strideA; p.W = W; p.ldw = ldw; p.bias = bias; p.res = res; p.ldres = N; p.strideRes = strideRes;
+    p.Cf = out_f32; p.ldcf = N; p.strideCf = strideCf; p.Cb = out_bf16; p.ldcb = N; p.strideCb = strideCb;
+    p.M = M; p.N = N; p.K = K; p.act = act; p.w_kpad = w_kpad; p.batch = batch;
+    return kcheck(launch_gemm(p, (hipStream_t)stream));
+}
 
 // ------------------------------------------------------------------------------------------------ exact-precision (fp32) kernels (exact.hip)
 // The launchers the engine's exact mode calls, as they stand; the checks here only keep divisors and the batch count positive.

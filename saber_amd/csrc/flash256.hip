@@ -25,16 +25,22 @@ __device__ __forceinline__ op16x8 f2_pack8(float a0, float a1, float a2, float a
 #define F2_STAGE (2 * F2_KB * F2_ROWB)         // K tile + V tile
 #define F2_LDS (2 * F2_STAGE)
 
-// Opart [q-block][split][64][256] fp32 un-normalised, ML [q-block][split][64][2] (running max in the exp2 domain, sum)
+// Opart [object][q-block][split][64][256] fp32 un-normalised, ML [object][q-block][split][64][2] (running max in the exp2 domain, sum).
+// blockIdx.y = object of a batch of independent problems of one shape (FlashBatch: element strides, a Q stride of 0 shares the queries);
+// an object's arithmetic does not depend on the batch it runs in.
+struct FlashBatch { int64_t q, k, v, o; int qblocks; };
 __global__ __launch_bounds__(512) void flash256_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, int n_keys,
                                                       float qscale, int split, const float* __restrict__ bias_v, bf16_t* __restrict__ out,
-                                                      float* __restrict__ Opart, float* __restrict__ ML) {
+                                                      float* __restrict__ Opart, float* __restrict__ ML, FlashBatch fb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qt = wave & 3, kh = wave >> 2;
     const int fi = lane & 15, fg = lane >> 4;
     const int qb = blockIdx.x / split, sp = blockIdx.x - qb * split;
+    const int64_t ob = blockIdx.y;
+    Q += ob * fb.q; K += ob * fb.k; V += ob * fb.v; out += ob * fb.o;
+    const int64_t wq = ob * fb.qblocks + qb;          // this workgroup's q-block within the batch's workspace
     const int nkb_all = (n_keys + F2_KB - 1) / F2_KB;
     const int per = (nkb_all + split - 1) / split;
     const int kb0 = sp * per, nkb = max(0, min(per, nkb_all - kb0));
@@ -160,14 +166,14 @@ __global__ __launch_bounds__(512) void flash256_kernel(const bf16_t* __restrict_
         const float a1 = exp2f(m - mn), a2 = exp2f(m2 - mn);
         const int q = q0 + qt * 16 + fi;
         if (split > 1) {
-            float* op = Opart + (((int64_t)qb * split + sp) * 64 + qt * 16 + fi) * 256;
+            float* op = Opart + ((wq * split + sp) * 64 + qt * 16 + fi) * 256;
 #pragma unroll
             for (int dt = 0; dt < 16; ++dt) {
                 const float4 t = *reinterpret_cast<const float4*>(mo + fi * 260 + 16 * dt + 4 * fg);
                 *reinterpret_cast<float4*>(op + 16 * dt + 4 * fg) = make_float4(o[dt][0] * a1 + t.x * a2, o[dt][1] * a1 + t.y * a2, o[dt][2] * a1 + t.z * a2, o[dt][3] * a1 + t.w * a2);
             }
             if (fg == 0) {
-                float* mlp = ML + (((int64_t)qb * split + sp) * 64 + qt * 16 + fi) * 2;
+                float* mlp = ML + ((wq * split + sp) * 64 + qt * 16 + fi) * 2;
                 mlp[0] = mn;
                 mlp[1] = l * a1 + l2 * a2;
             }
@@ -185,21 +191,23 @@ __global__ __launch_bounds__(512) void flash256_kernel(const bf16_t* __restrict_
     }
 }
 
-// out[q] = bf16(sum_s w_s Opart[q][s] / L + bias), w_s = 2^(m_s - max m), L = sum_s w_s l_s; one block per 4 query rows
+// out[q] = bf16(sum_s w_s Opart[q][s] / L + bias), w_s = 2^(m_s - max m), L = sum_s w_s l_s; one block per 4 query rows, blockIdx.y = object
 __global__ __launch_bounds__(256) void flash256_combine_kernel(const float* __restrict__ Opart, const float* __restrict__ ML, int split, const float* __restrict__ bias_v,
-                                                              bf16_t* __restrict__ out, int n_q) {
+                                                              bf16_t* __restrict__ out, int n_q, int64_t o_stride) {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= n_q) return;
-    const int qb = q >> 6, r = q & 63;
+    out += (int64_t)blockIdx.y * o_stride;
+    const int64_t qb = (int64_t)blockIdx.y * (n_q >> 6) + (q >> 6);
+    const int r = q & 63;
     float mm = -3.0e38f;
-    for (int s = 0; s < split; ++s) mm = fmaxf(mm, ML[(((int64_t)qb * split + s) * 64 + r) * 2]);
+    for (int s = 0; s < split; ++s) mm = fmaxf(mm, ML[((qb * split + s) * 64 + r) * 2]);
     float L = 0.f;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int s = 0; s < split; ++s) {
-        const float* mlp = ML + (((int64_t)qb * split + s) * 64 + r) * 2;
+        const float* mlp = ML + ((qb * split + s) * 64 + r) * 2;
         const float w = exp2f(mlp[0] - mm);
         L += w * mlp[1];
-        const float4 t = *reinterpret_cast<const float4*>(Opart + (((int64_t)qb * split + s) * 64 + r) * 256 + 4 * lane);
+        const float4 t = *reinterpret_cast<const float4*>(Opart + ((qb * split + s) * 64 + r) * 256 + 4 * lane);
         acc.x += w * t.x; acc.y += w * t.y; acc.z += w * t.z; acc.w += w * t.w;
     }
     const float inv = 1.0f / L;
@@ -207,21 +215,47 @@ __global__ __launch_bounds__(256) void flash256_combine_kernel(const float* __re
     *reinterpret_cast<uint2*>(out + (int64_t)q * 256 + 4 * lane) = make_uint2(pack_op16(acc.x * inv + b.x, acc.y * inv + b.y), pack_op16(acc.z * inv + b.z, acc.w * inv + b.w));
 }
 
-const char* launch_flash256(const bf16_t* Q, const bf16_t* K, const bf16_t* V, int n_q, int n_keys, float scale, const float* bias_v, bf16_t* out, float* ws,
-                            size_t ws_floats, hipStream_t s) {
-    if (n_q <= 0 || (n_q & 63) || n_keys <= 0 || !Q || !K || !V || !bias_v || !out) return "flash256: bad argument (n_q must be a multiple of 64)";
-    const int qblocks = n_q / 64, nkb = (n_keys + F2_KB - 1) / F2_KB;
+// the split over the keys of ONE problem of n_q / n_keys: it fixes the summation order, so the batched launcher must not let the batch change it
+static int flash256_split(int qblocks, int nkb) {
     int split = 1;
     while (qblocks * split < 256 && split * 2 <= nkb && split < 8) split *= 2;
-    if (split > 1 && (!ws || ws_floats < (size_t)qblocks * split * 64 * 258)) split = 1;
+    return split;
+}
+static const char* flash256_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, int n_q, int n_keys, int batch, FlashBatch fb, int split, float scale,
+                                   const float* bias_v, bf16_t* out, float* ws, hipStream_t s) {
+    const int qblocks = n_q / 64;
     float* Opart = ws;
-    float* ML = ws ? ws + (size_t)qblocks * split * 64 * 256 : nullptr;
+    float* ML = ws ? ws + (size_t)batch * qblocks * split * 64 * 256 : nullptr;
     static bool attr = false;
     if (!attr) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(flash256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F2_LDS) != hipSuccess) return "flash256: cannot reserve LDS";
         attr = true;
     }
-    hipLaunchKernelGGL(flash256_kernel, dim3(qblocks * split), dim3(512), F2_LDS, s, Q, K, V, n_keys, scale * 1.4426950408889634f, split, bias_v, out, Opart, ML);
-    if (split > 1) hipLaunchKernelGGL(flash256_combine_kernel, dim3((n_q + 3) / 4), dim3(256), 0, s, (const float*)Opart, (const float*)ML, split, bias_v, out, n_q);
+    fb.qblocks = qblocks;
+    hipLaunchKernelGGL(flash256_kernel, dim3(qblocks * split, batch), dim3(512), F2_LDS, s, Q, K, V, n_keys, scale * 1.4426950408889634f, split, bias_v, out, Opart, ML, fb);
+    if (split > 1)
+        hipLaunchKernelGGL(flash256_combine_kernel, dim3((n_q + 3) / 4, batch), dim3(256), 0, s, (const float*)Opart, (const float*)ML, split, bias_v, out, n_q, fb.o);
     return nullptr;
+}
+
+const char* launch_flash256(const bf16_t* Q, const bf16_t* K, const bf16_t* V, int n_q, int n_keys, float scale, const float* bias_v, bf16_t* out, float* ws,
+                            size_t ws_floats, hipStream_t s) {
+    if (n_q <= 0 || (n_q & 63) || n_keys <= 0 || !Q || !K || !V || !bias_v || !out) return "flash256: bad argument (n_q must be a multiple of 64)";
+    const int qblocks = n_q / 64, nkb = (n_keys + F2_KB - 1) / F2_KB;
+    int split = flash256_split(qblocks, nkb);
+    if (split > 1 && (!ws || ws_floats < (size_t)qblocks * split * 64 * 258)) split = 1;
+    return flash256_launch(Q, K, V, n_q, n_keys, 1, FlashBatch{0, 0, 0, 0, qblocks}, split, scale, bias_v, out, ws, s);
+}
+
+const char* launch_flash256_batched(const bf16_t* Q, int64_t q_stride, const bf16_t* K, int64_t k_stride, const bf16_t* V, int64_t v_stride, int n_q, int n_keys,
+                                    int batch, float scale, const float* bias_v, bf16_t* out, int64_t o_stride, float* ws, size_t ws_floats, hipStream_t s) {
+    if (n_q <= 0 || (n_q & 63) || n_keys <= 0 || !Q || !K || !V || !bias_v || !out) return "flash256_batched: bad argument (n_q must be a multiple of 64)";
+    if (batch <= 0 || batch > 65535) return "flash256_batched: batch must be in 1..65535";
+    if (q_stride < 0 || k_stride < 0 || v_stride < 0 || (batch > 1 && o_stride < (int64_t)n_q * 256)) return "flash256_batched: bad stride (outputs must not overlap)";
+    if ((q_stride | k_stride | v_stride | o_stride) & 7) return "flash256_batched: strides must be multiples of 8 elements";
+    const int qblocks = n_q / 64, nkb = (n_keys + F2_KB - 1) / F2_KB;
+    int split = flash256_split(qblocks, nkb);
+    if (split > 1 && !ws) split = 1;          // no workspace: no split, as launch_flash256
+    if (split > 1 && ws_floats < (size_t)batch * qblocks * split * 64 * 258) return "flash256_batched: workspace too small for batch * (n_q / 64) * split * 64 * 258 floats";
+    return flash256_launch(Q, K, V, n_q, n_keys, batch, FlashBatch{q_stride, k_stride, v_stride, o_stride, qblocks}, split, scale, bias_v, out, ws, s);
 }

@@ -208,6 +208,7 @@ SABER_OP_FWD(launch_mask_post) SABER_OP_FWD(launch_gather_masks) SABER_OP_FWD(la
 SABER_OP_FWD(launch_rope) SABER_OP_FWD(launch_softmax_rows) SABER_OP_FWD(launch_conv3x3s2) SABER_OP_FWD(launch_unpack_masks) SABER_OP_FWD(launch_paint_nearest)
 SABER_OP_FWD(launch_conv3x3s2_t) SABER_OP_FWD(launch_dwconv7_t) SABER_OP_FWD(launch_dwconv7) SABER_OP_FWD(launch_conv4x4s4) SABER_OP_FWD(launch_resize_plane)
 SABER_OP_FWD(launch_flash256) SABER_OP_FWD(launch_gauss_mirror) SABER_OP_FWD(launch_axpy) SABER_OP_FWD(launch_bf16_to_f32)
+SABER_OP_FWD(launch_rope_batched) SABER_OP_FWD(launch_flash256_batched) SABER_OP_FWD(launch_membank_assemble)
 #undef SABER_OP_FWD
 #undef SABER_OP_INIT
 #endif

@@ -97,6 +97,8 @@ const char* launch_pair_intersections(const uint32_t* bits, int n, int64_t words
 const char* launch_unpermute_nchw(const float* tok, int C, int stage, float* out, hipStream_t s);
 // ------------------------------------------------------------------ video_ops.hip (SAM2 memory path, channels-last fp32, row-major pixels)
 const char* launch_rope(const float* x, int64_t rows, int n_rot, int C, int side, float theta, float* out_f, bf16_t* out_bf, hipStream_t s);
+// launch_rope over `batch` stacked blocks of rows_per rows: a row rotates when row % rows_per < n_rot, with the token of row % rows_per
+const char* launch_rope_batched(const float* x, int64_t rows_per, int batch, int n_rot, int C, int side, float theta, float* out_f, bf16_t* out_bf, hipStream_t s);
 const char* launch_softmax_rows(const float* S, int64_t lds_, int64_t rows, int n, float scale, bf16_t* P, int64_t ldp, hipStream_t s);
 const char* launch_conv3x3s2(const float* in, int H, int W, int Cin, const float* w, const float* b, int Cout, float* out, hipStream_t s);
 const char* launch_unpack_masks(const uint32_t* bits, int n, int H, int W, uint8_t* out, hipStream_t s);
@@ -110,6 +112,18 @@ const char* launch_resize_plane(const float* in, int n_planes, int H, int W, flo
 // row-major, out bf16 [n_q][256]; ws: >= (n_q / 64) * 8 * 64 * 258 floats of scratch for the split over the keys (may be NULL: no split)
 const char* launch_flash256(const bf16_t* Q, const bf16_t* K, const bf16_t* V, int n_q, int n_keys, float scale, const float* bias_v, bf16_t* out, float* ws,
                             size_t ws_floats, hipStream_t s);
+// launch_flash256 for `batch` independent problems of one shape: object b reads Q + b * q_stride (0: shared queries), K + b * k_stride,
+// V + b * v_stride and writes out + b * o_stride (strides in elements).  The split over the keys is the one launch_flash256 picks for ONE problem
+// of n_q / n_keys, so every object's result is that call's bits; ws: batch * (n_q / 64) * split * 64 * 258 floats (NULL: no split; too small: an error)
+const char* launch_flash256_batched(const bf16_t* Q, int64_t q_stride, const bf16_t* K, int64_t k_stride, const bf16_t* V, int64_t v_stride, int n_q, int n_keys,
+                                    int batch, float scale, const float* bias_v, bf16_t* out, int64_t o_stride, float* ws, size_t ws_floats, hipStream_t s);
 const char* launch_gauss_mirror(const float* in, float* out, int n_planes, int H, int W, int axis, double sigma, hipStream_t s);
 const char* launch_axpy(const float* x, const float* y, const float* g, float alpha, int64_t rows, int C, float* out, hipStream_t s);
 const char* launch_bf16_to_f32(const bf16_t* x, int64_t n, float* out, hipStream_t s);
+// memory bank of `batch` tracked objects in one pass (video_ops.hip: membank_assemble_kernel).  mems: batch * n_mem HOST pointers to stored
+// (4096, 64) 16-bit memories, pos_idx: batch * n_mem HOST indices into pos_tables [n_tables][4096][64] fp32; ptr_tok / ptr_pos: (n_ptr_rows, 64)
+// pointer-token rows per object (16-bit) and their fp32 positions (a stride of 0 shares them).  mem_out / kin_out: [batch][Nkp][64],
+// Nkp = (4096 n_mem + n_ptr_rows) rounded up to 64: the stored bits, and pack_op16(float(mem) + pos); pad rows zero
+const char* launch_membank_assemble(const bf16_t* const* mems, const int* pos_idx, int n_mem, const float* pos_tables, int n_tables, const bf16_t* ptr_tok,
+                                    int64_t ptr_tok_stride, const float* ptr_pos, int64_t ptr_pos_stride, int n_ptr_rows, int batch, bf16_t* mem_out, bf16_t* kin_out,
+                                    hipStream_t s);

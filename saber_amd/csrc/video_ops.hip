@@ -49,6 +49,111 @@ const char* launch_rope(const float* x, int64_t rows, int n_rot, int C, int side
     return nullptr;
 }
 
+// The same for `batch` stacked blocks of rows_per rows (the keys of several objects' memory banks: each bank's pointer-token rows are
+// copied, not rotated): a row rotates when row % rows_per < n_rot and takes its token from row % rows_per.  Per element the arithmetic is
+// rope_kernel's.
+__global__ __launch_bounds__(256) void rope_batched_kernel(const float* __restrict__ x, int64_t rows, int64_t rows_per, int n_rot, int C, int side, float theta,
+                                                           float* __restrict__ out_f, bf16_t* __restrict__ out_bf) {
+    const int half = C >> 1, quarter = C >> 2;
+    const int64_t total = rows * half;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t row = idx / half;
+        const int i = (int)(idx - row * half);
+        const int64_t rr = row % rows_per;
+        float a = x[row * C + 2 * i], b = x[row * C + 2 * i + 1];
+        if (rr < n_rot) {
+            const int tok = (int)(rr % ((int64_t)side * side));
+            const int coord = i < quarter ? tok % side : tok / side;
+            const int fi = i < quarter ? i : i - quarter;
+            const float freq = 1.0f / powf(theta, (float)(4 * fi) / (float)C);
+            float sn, cs;
+            sincosf((float)coord * freq, &sn, &cs);
+            const float ra = a * cs - b * sn, rb = b * cs + a * sn;
+            a = ra; b = rb;
+        }
+        if (out_f) { out_f[row * C + 2 * i] = a; out_f[row * C + 2 * i + 1] = b; }
+        if (out_bf) *reinterpret_cast<uint32_t*>(out_bf + row * C + 2 * i) = pack_op16(a, b);
+    }
+}
+const char* launch_rope_batched(const float* x, int64_t rows_per, int batch, int n_rot, int C, int side, float theta, float* out_f, bf16_t* out_bf, hipStream_t s) {
+    if (rows_per <= 0 || batch <= 0) return nullptr;
+    if (C & 3) return "rope_batched: C must be a multiple of 4";
+    if (side <= 0 || n_rot < 0) return "rope_batched: side must be positive and n_rot non-negative";
+    const int64_t rows = rows_per * batch, total = rows * (C >> 1);
+    hipLaunchKernelGGL(rope_batched_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s, x, rows, rows_per, n_rot, C, side, theta, out_f, out_bf);
+    return nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------ memory bank of a batch of objects
+// mem[b][r][:] = the stored 16-bit rows of object b's bank: its n_mem spatial memories (4096 rows each), then its pointer-token rows;
+// kin[b][r][:] = pack_op16(float(mem) + pos): the position row comes from pos_tables[idx] for a spatial memory and from ptr_pos for a
+// pointer token (the arithmetic of bf16_to_f32_kernel + add_to_bf16_kernel).  Rows Nk..Nkp of both are zero.  A block owns 32 rows x 8
+// 16-byte vectors; 4096 is a multiple of 32, so the memory a block reads is uniform: its pointer comes out of the kernel arguments with
+// scalar loads.  The pointers of up to MB_CHUNK objects travel by value.
+#define MB_CHUNK 16
+#define MB_MAX_MEM 7
+struct MembankArgs {
+    const bf16_t* mem[MB_CHUNK][MB_MAX_MEM];
+    int pos_idx[MB_CHUNK][MB_MAX_MEM];
+};
+__global__ __launch_bounds__(256) void membank_assemble_kernel(MembankArgs args, int n_mem, const float* __restrict__ pos_tables, const bf16_t* __restrict__ ptr_tok,
+                                                               int64_t ptr_tok_stride, const float* __restrict__ ptr_pos, int64_t ptr_pos_stride, int n_ptr_rows,
+                                                               int Nkp, int obj0, bf16_t* __restrict__ mem_out, bf16_t* __restrict__ kin_out) {
+    const int ob = blockIdx.y;
+    const int r0 = blockIdx.x * 32;                          // uniform
+    const int r = r0 + (threadIdx.x >> 3), c = (threadIdx.x & 7) * 8;
+    const int n_spatial = n_mem * 4096;
+    uint4 m = make_uint4(0u, 0u, 0u, 0u), k = make_uint4(0u, 0u, 0u, 0u);
+    const float* pp = nullptr;
+    if (r0 < n_spatial) {
+        const int j = r0 >> 12;
+        const int64_t off = (int64_t)(r & 4095) * 64 + c;
+        m = *reinterpret_cast<const uint4*>(args.mem[ob][j] + off);
+        pp = pos_tables + (int64_t)args.pos_idx[ob][j] * 4096 * 64 + off;
+    } else if (r < n_spatial + n_ptr_rows) {
+        const int64_t off = (int64_t)(r - n_spatial) * 64 + c;
+        m = *reinterpret_cast<const uint4*>(ptr_tok + (int64_t)(obj0 + ob) * ptr_tok_stride + off);
+        pp = ptr_pos + (int64_t)(obj0 + ob) * ptr_pos_stride + off;
+    }
+    if (pp) {
+        const float4 p0 = *reinterpret_cast<const float4*>(pp), p1 = *reinterpret_cast<const float4*>(pp + 4);
+        k.x = pack_op16(op2f((bf16_t)(m.x & 0xffffu)) + p0.x, op2f((bf16_t)(m.x >> 16)) + p0.y);
+        k.y = pack_op16(op2f((bf16_t)(m.y & 0xffffu)) + p0.z, op2f((bf16_t)(m.y >> 16)) + p0.w);
+        k.z = pack_op16(op2f((bf16_t)(m.z & 0xffffu)) + p1.x, op2f((bf16_t)(m.z >> 16)) + p1.y);
+        k.w = pack_op16(op2f((bf16_t)(m.w & 0xffffu)) + p1.z, op2f((bf16_t)(m.w >> 16)) + p1.w);
+    }
+    const int64_t o = ((int64_t)(obj0 + ob) * Nkp + r) * 64 + c;
+    *reinterpret_cast<uint4*>(mem_out + o) = m;
+    *reinterpret_cast<uint4*>(kin_out + o) = k;
+}
+const char* launch_membank_assemble(const bf16_t* const* mems, const int* pos_idx, int n_mem, const float* pos_tables, int n_tables, const bf16_t* ptr_tok,
+                                    int64_t ptr_tok_stride, const float* ptr_pos, int64_t ptr_pos_stride, int n_ptr_rows, int batch, bf16_t* mem_out, bf16_t* kin_out,
+                                    hipStream_t s) {
+    if (batch <= 0) return nullptr;
+    if (n_mem < 0 || n_mem > MB_MAX_MEM || n_ptr_rows < 0 || n_mem + n_ptr_rows == 0) return "membank_assemble: 0..7 memories, n_ptr_rows >= 0, not both zero";
+    if (!mem_out || !kin_out || (n_mem && (!mems || !pos_idx || !pos_tables)) || (n_ptr_rows && (!ptr_tok || !ptr_pos))) return "membank_assemble: null pointer";
+    if (ptr_tok_stride < 0 || ptr_pos_stride < 0 || ((ptr_tok_stride | ptr_pos_stride) & 7)) return "membank_assemble: pointer-token strides must be non-negative multiples of 8";
+    if (((uintptr_t)mem_out | (uintptr_t)kin_out | (uintptr_t)pos_tables | (uintptr_t)ptr_tok | (uintptr_t)ptr_pos) & 15) return "membank_assemble: buffers must be 16-byte aligned";
+    for (int i = 0; i < batch * n_mem; ++i) {
+        if (!mems[i] || ((uintptr_t)mems[i] & 15)) return "membank_assemble: a memory pointer is null or not 16-byte aligned";
+        if (pos_idx[i] < 0 || pos_idx[i] >= n_tables) return "membank_assemble: position-table index out of range";
+    }
+    const int Nk = n_mem * 4096 + n_ptr_rows, Nkp = (Nk + 63) / 64 * 64;
+    for (int b0 = 0; b0 < batch; b0 += MB_CHUNK) {
+        const int nb = std::min(MB_CHUNK, batch - b0);
+        MembankArgs a;
+        for (int b = 0; b < MB_CHUNK; ++b)
+            for (int j = 0; j < MB_MAX_MEM; ++j) {
+                const bool live = b < nb && j < n_mem;
+                a.mem[b][j] = live ? mems[(size_t)(b0 + b) * n_mem + j] : nullptr;
+                a.pos_idx[b][j] = live ? pos_idx[(size_t)(b0 + b) * n_mem + j] : 0;
+            }
+        hipLaunchKernelGGL(membank_assemble_kernel, dim3(Nkp / 32, nb), dim3(256), 0, s, a, n_mem, pos_tables, ptr_tok, ptr_tok_stride, ptr_pos, ptr_pos_stride, n_ptr_rows,
+                           Nkp, b0, mem_out, kin_out);
+    }
+    return nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------ row softmax
 // P[row][0..n) = softmax(scale * S[row][0..n)) as bf16, columns n..ldp are written as zeros (key padding for the PV product)
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ S, int64_t lds_, int n, float scale, bf16_t* __restrict__ P, int64_t ldp) {

@@ -123,6 +123,7 @@ class saber3D(saber2D):
         self.confidence_debug = False
         self.nframes = None
         self.filter_threshold = 0.5
+        self.batch_objects = False          # True: the tracked objects of a frame share one batched memory attention (SAM2Adapter.segment_volume(batch_objects=True)); same result
         self.device_volumes = False         # True: propagated label volumes stay on self.device (utils/labelvol.py, csrc/labelvol.hip); the segmenters' merges run there
 
     def propagate(self, mask_shape, target_class: Optional[int] = 1):
@@ -130,6 +131,8 @@ class saber3D(saber2D):
         as the adapter's device tensor (SAM2Adapter.segment_volume(device_volume=True)) instead of a numpy array."""
         arrays = [m["segmentation"] for m in self.masks] if isinstance(self.masks[0], dict) else self.masks
         route = {"device_volume": True} if self.device_volumes else {}
+        if self.batch_objects:
+            route["batch_objects"] = True
         vol = self.video_predictor.segment_volume(start_frame_idx=self.ann_frame_idx, masks=arrays, vol_shape=mask_shape,
                                                   max_frame_num_to_track=self.nframes, min_presence_score=self.filter_threshold, **route)
         self.video_predictor.reset_state()
