@@ -27,7 +27,7 @@
  *   saber_smooth_labels / saber_gaussian_smoothing_3d
  *       <- fast_3d_gaussian_smoothing(volume, scale, deviceID)        saber/filters/masks.py:230-287
  *          gaussian_smoothing_3d(volume, sigma, device)               saber/filters/gaussian.py:76-138
- *   saber_consensus_components
+ *   saber_consensus_components, saber_consensus_components_bits, saber_relabel_plane
  *       <- _consensus_based_resolution(image_shape, masks, confidences) saber/filters/masks.py:64-121
  *
  * Conventions: plain pointers and sizes only; every *_dev pointer is device memory owned by the
@@ -361,6 +361,16 @@ typedef struct saber_consensus_row {
 int saber_consensus_components(saber_engine* e, const uint8_t* masks_dev, int n, int H, int W, const int* select_host, const float* conf_host,
                                int k, int capacity, int32_t* labels_out_dev, saber_consensus_row* table_out_dev, int* out_n_components,
                                void* stream);
+/* The same on rows of the mask generator's bit-packed stack (saber_amg_generate): bits_dev (n_rows,H,W32) uint32, W32 = ceil(W / 32), bit b
+ * of word w of a row = pixel 32w+b; select_host indexes its rows.  Same arithmetic (the float32 chain over the set masks in list order),
+ * outputs, limits and capacity protocol; only the accumulation kernel reads another format, an eighth of the bytes. */
+int saber_consensus_components_bits(saber_engine* e, const uint32_t* bits_dev, int n_rows, int H, int W, const int* select_host,
+                                    const float* conf_host, int k, int capacity, int32_t* labels_out_dev, saber_consensus_row* table_out_dev,
+                                    int* out_n_components, void* stream);
+/* plane_dev[p] = lut_dev[labels_dev[p]] over an (H,W) int32 label plane (0 for a label outside [0, lut_len)): paints the components of a
+ * consensus call with the values of a caller-built table, lut[0] = 0.  All three on the engine's device; no synchronisation. */
+int saber_relabel_plane(saber_engine* e, const int32_t* labels_dev, int H, int W, const uint16_t* lut_dev, int lut_len, uint16_t* plane_dev,
+                        void* stream);
 
 /* ---- domain-expert classifier filter on the engine's image embeddings ----
  * Replaces saber.classifier.models.predictor.Predictor (saber/classifier/models/predictor.py:9-60 construction, :117-175 predict) with the
@@ -382,10 +392,16 @@ int saber_classifier_finalize(saber_classifier* c);
  * Synchronises the stream (bounding boxes, areas and the probabilities come back to the host). */
 int saber_classifier_predict(saber_classifier* c, const float* image_dev, int H, int W, const uint8_t* masks_dev, int n, int min_area,
                              float* probs_host, void* stream);
+/* saber_classifier_predict on rows rows_host[0..k) (a HOST array, 0 <= row < n_rows) of the mask generator's bit-packed stack bits_dev
+ * (n_rows,H,W32) uint32, bit b of word w of a row = pixel 32w+b (bits past W in a row's last word are ignored).  Same semantics and the
+ * same bits as saber_classifier_predict on the unpacked (k,H,W) stack of those rows: only the bounding-box kernel and the crop kernel's
+ * nearest-neighbour mask tap read the other format.  probs_host: (k, num_classes).  No (k,H,W) uint8 stack is made. */
+int saber_classifier_predict_bits(saber_classifier* c, const float* image_dev, int H, int W, const uint32_t* bits_dev, int n_rows,
+                                  const int* rows_host, int k, int min_area, float* probs_host, void* stream);
 /* SAM2Classifier.forward after the backbone, on the embeddings engine slots 0..k-1 hold now (saber_encode / saber_set_embed_tokens):
  * mask_crops_dev (k,320,320) uint8 -> probs_host (k, num_classes). */
 int saber_classifier_head(saber_classifier* c, const uint8_t* mask_crops_dev, int k, float* probs_host, void* stream);
-/* The 320x320 image crops / binarised mask crops the last saber_classifier_predict call made for its first n masks (device copies). */
+/* The 320x320 image crops / binarised mask crops the last saber_classifier_predict / _predict_bits call made for its first n masks (device copies). */
 int saber_classifier_get_crops(saber_classifier* c, int n, float* crops_out_dev, uint8_t* masks_out_dev, void* stream);
 
 /* Per-launch HIP-event profiling of the engine's own kernels, by kernel class (events are recorded on the

@@ -99,11 +99,14 @@ SIGNATURES = {
     "saber_refine_membranes_instances": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "saber_label_statistics": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_i), _vp]),
     "saber_consensus_components": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_f), _i, _i, _vp, _vp, C.POINTER(_i), _vp]),
+    "saber_consensus_components_bits": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_f), _i, _i, _vp, _vp, C.POINTER(_i), _vp]),
+    "saber_relabel_plane": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "saber_classifier_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "saber_classifier_destroy": (None, [_vp]),
     "saber_classifier_set_weight": (_i, [_vp, C.c_char_p, _vp, _i64p, _i]),
     "saber_classifier_finalize": (_i, [_vp]),
     "saber_classifier_predict": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "saber_classifier_predict_bits": (_i, [_vp, _vp, _i, _i, _vp, _i, C.POINTER(_i), _i, _i, _vp, _vp]),
     "saber_classifier_head": (_i, [_vp, _vp, _i, _vp, _vp]),
     "saber_classifier_get_crops": (_i, [_vp, _i, _vp, _vp, _vp]),
     "saber_profile_begin": (_i, [_vp]),

@@ -42,6 +42,9 @@ class Predictor:
         self.device = engine.device
         if head_weights is None:
             head_weights = load_head_weights(model_weights)
+        # kept (as float32 copies) for replica(): a second in-flight slice needs a classifier on its own engine handle
+        self.head_weights = {k: np.array(v, dtype=np.float32) for k, v in head_weights.items() if not k.endswith("num_batches_tracked")}
+        self._replicas = {}
         self.lib = engine.lib
         h = C.c_void_p()
         engine._check(self.lib.saber_classifier_create(engine.h, self.num_classes, C.byref(h)))
@@ -54,7 +57,21 @@ class Predictor:
             engine._check(self.lib.saber_classifier_set_weight(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
         engine._check(self.lib.saber_classifier_finalize(self.h))
 
+    def replica(self, engine) -> "Predictor":
+        """The same classifier (config, head weights, min_area) on another engine handle, cached per handle.  A classifier's device
+        buffers and the encoder slots it fills belong to its engine handle, so two threads never share one Predictor: the z-loop's thread
+        w > 0 uses replica(<engine handle w>)."""
+        if engine is self.engine:
+            return self
+        key = id(engine)
+        if key not in self._replicas:
+            self._replicas[key] = Predictor(None, None, min_area=self.min_area, config=self.config, head_weights=self.head_weights, engine=engine)
+        return self._replicas[key]
+
     def close(self):
+        for r in getattr(self, "_replicas", {}).values():
+            r.close()
+        self._replicas = {}
         if getattr(self, "h", None):
             self.lib.saber_classifier_destroy(self.h)
             self.h = None
@@ -99,6 +116,47 @@ class Predictor:
         out = np.zeros((total, self.num_classes), dtype=np.float32)
         for s in range(0, total, batch_size):
             out[s:s + batch_size] = self.predict(image, masks[s:s + batch_size])
+        return out
+
+    # ---- the device-resident slice pipeline: masks stay the mask generator's bit-packed rows
+    @torch.inference_mode()
+    def predict_bits(self, image, bits: torch.Tensor, rows, W: int) -> np.ndarray:
+        """predict on rows `rows` (in that order) of a bit-packed (n,H,W32) int32 device stack (Engine.amg_generate; bit b of word w =
+        pixel 32w+b; W = image width): the same (len(rows), num_classes) array predict returns for the unpacked stack of those rows,
+        without that stack (include/saber_amd.h: saber_classifier_predict_bits)."""
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32))
+        image = image.to(self.device, dtype=torch.float32).contiguous()
+        W = int(W)
+        if not isinstance(bits, torch.Tensor) or not bits.is_cuda or bits.device != self.device or bits.dtype not in (torch.int32, torch.uint32):
+            raise ValueError("Predictor.predict_bits expects the bit-packed masks as an int32 tensor on the classifier's device")
+        if image.ndim != 2 or bits.ndim != 3 or int(image.shape[1]) != W or tuple(bits.shape[1:]) != (int(image.shape[0]), (W + 31) // 32):
+            raise ValueError(f"Predictor.predict_bits expects an (H,W) image and (n,H,ceil(W/32)) masks, got {tuple(image.shape)} and {tuple(bits.shape)}")
+        bits = bits.contiguous()
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        k, n = int(r.size), int(bits.shape[0])
+        probs = np.zeros((k, self.num_classes), dtype=np.float32)
+        if k == 0:
+            return probs
+        if r.min() < 0 or r.max() >= n:
+            raise ValueError(f"Predictor.predict_bits: rows must lie in [0, {n}), got {int(r.min())}..{int(r.max())}")
+        r = r.astype(np.int32)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self.engine._check(self.lib.saber_classifier_predict_bits(self.h, C.c_void_p(image.data_ptr()), int(image.shape[0]), W, C.c_void_p(bits.data_ptr()),
+                                                                  n, r.ctypes.data_as(C.POINTER(C.c_int)), k, int(self.min_area),
+                                                                  probs.ctypes.data_as(C.c_void_p), stream))
+        return probs
+
+    @torch.inference_mode()
+    def batch_predict_bits(self, image, bits: torch.Tensor, rows, W: int, batch_size: int = 32) -> np.ndarray:
+        """batch_predict on bit-packed rows: groups of batch_size rows, each one predict_bits call (the whole-image statistics are
+        recomputed per group, as batch_predict does)."""
+        r = np.asarray(rows, dtype=np.int64).reshape(-1)
+        out = np.zeros((r.size, self.num_classes), dtype=np.float32)
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(self.device)
+        for s in range(0, r.size, batch_size):
+            out[s:s + batch_size] = self.predict_bits(image, bits, r[s:s + batch_size], W)
         return out
 
     # ---- test / inspection access

@@ -36,6 +36,7 @@ struct saber_classifier {
     float *fc1w = nullptr, *fc1b = nullptr, *lng = nullptr, *lnb = nullptr, *fc2w = nullptr, *fc2b = nullptr;
     // per-call workspaces (grown on demand)
     int *bbox = nullptr, *boxes = nullptr, *areas = nullptr, *sel = nullptr; size_t cap_n = 0;
+    int* rows = nullptr; size_t cap_rows = 0;                    // predict_bits: the selected rows of the bit-packed stack
     double* sums = nullptr;
     float* crops = nullptr; uint8_t* cmask = nullptr;
     bf16_t *A0 = nullptr, *A1 = nullptr, *A2 = nullptr; float *G1 = nullptr, *G2 = nullptr, *G3 = nullptr, *probs = nullptr; size_t cap_b = 0;
@@ -55,6 +56,38 @@ static inline bf16_t cls_f2bf(float f) {
 __global__ void cls_bbox_init_kernel(int* bbox, int n, int H, int W) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { bbox[4 * i] = H; bbox[4 * i + 1] = -1; bbox[4 * i + 2] = W; bbox[4 * i + 3] = -1; }
+}
+// Where the masks of a predict call live.  at(b, y, x): is pixel (y, x) of the call's mask b set?  Everything that does not read a mask
+// (statistics, crop windows, the bilinear image taps, encoder, head) is the same code for both.
+struct ClsByteMasks {                        // (n,H,W) uint8, non-zero = set
+    const uint8_t* p; int H, W;
+    __device__ __forceinline__ bool at(int b, int y, int x) const { return p[((int64_t)b * H + y) * W + x] != 0; }
+};
+struct ClsBitMasks {                         // rows[b] of an (n_rows,H,W32) bit-packed stack, bit i of word w = pixel 32w+i
+    const uint32_t* p; const int* rows; int H, W32;
+    __device__ __forceinline__ bool at(int b, int y, int x) const {
+        return (p[((int64_t)rows[b] * H + y) * W32 + (x >> 5)] >> (x & 31)) & 1u;
+    }
+};
+// one wave per (row y, mask b) of a bit-packed stack: a word's first and last set bit give its min and max x; the row's last word is
+// masked to W, so bits past the image never widen a box
+__global__ __launch_bounds__(256) void cls_bbox_bits_kernel(ClsBitMasks m, int H, int W, int* __restrict__ bbox) {
+    const int b = blockIdx.y, y = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (y >= H) return;                                           // wave-uniform
+    const uint32_t* row = m.p + ((int64_t)m.rows[b] * H + y) * m.W32;
+    int xmin = W, xmax = -1;
+    for (int w = lane; w < m.W32; w += 64) {
+        uint32_t wd = row[w];
+        const int left = W - 32 * w;                               // pixels of the image from this word's first one on: >= 1
+        if (left < 32) wd &= (1u << left) - 1u;
+        if (wd) { xmin = min(xmin, 32 * w + __builtin_ctz(wd)); xmax = max(xmax, 32 * w + 31 - __builtin_clz(wd)); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { xmin = min(xmin, __shfl_xor(xmin, o, 64)); xmax = max(xmax, __shfl_xor(xmax, o, 64)); }
+    if (lane == 0 && xmax >= 0) {
+        atomicMin(&bbox[4 * b + 0], y); atomicMax(&bbox[4 * b + 1], y);
+        atomicMin(&bbox[4 * b + 2], xmin); atomicMax(&bbox[4 * b + 3], xmax);
+    }
 }
 // one block per (row y, mask b): [y_min, y_max, x_min, x_max] of the non-zero pixels
 __global__ __launch_bounds__(256) void cls_bbox_kernel(const uint8_t* __restrict__ masks, int H, int W, int* __restrict__ bbox) {
@@ -96,8 +129,9 @@ __device__ __forceinline__ void bil_tap(int o, int in, int out, int* i0, int* i1
     *i0 = i; *i1 = i + ((i + 1 > in - 1) ? 0 : 1);
 }
 // crop b = bilinear resize of the z-scored image window boxes[b] = (top, left, h, w) to 320x320; mask crop = nearest resize of the same
-// window, binarised; areas[b] = pixels of the mask crop
-__global__ __launch_bounds__(256) void cls_crop_kernel(const float* __restrict__ img, const uint8_t* __restrict__ masks, int H, int W,
+// window, binarised; areas[b] = pixels of the mask crop.  Masks: ClsByteMasks / ClsBitMasks, read by the one nearest-neighbour tap
+template <class Masks>
+__global__ __launch_bounds__(256) void cls_crop_kernel(const float* __restrict__ img, Masks masks, int H, int W,
                                                        const int* __restrict__ boxes, const double* __restrict__ sums, double npix,
                                                        float* __restrict__ crops, uint8_t* __restrict__ cmask, int* __restrict__ areas) {
     const int b = blockIdx.y;
@@ -120,7 +154,7 @@ __global__ __launch_bounds__(256) void cls_crop_kernel(const float* __restrict__
     // nearest: src = min(floor(dst * in / out), in - 1)
     const int ny = min((int)floorf((float)oy * ((float)h / (float)CROP)), h - 1);
     const int nx = min((int)floorf((float)ox * ((float)w / (float)CROP)), w - 1);
-    const int m = masks[((int64_t)b * H + top + ny) * W + left + nx] ? 1 : 0;
+    const int m = masks.at(b, top + ny, left + nx) ? 1 : 0;
     cmask[(int64_t)b * CROP_PIX + o] = (uint8_t)m;
     const unsigned long long ball = __ballot(m);
     if ((threadIdx.x & 63) == 0 && ball) atomicAdd(&areas[b], __popcll(ball));
@@ -391,15 +425,19 @@ static void cls_crop_box(const int* bb, int H, int W, int* out) {
     out[0] = top; out[1] = left; out[2] = std::min(ch, H); out[3] = std::min(cw, W);
 }
 
-extern "C" int saber_classifier_predict(saber_classifier* c, const float* image_dev, int H, int W, const uint8_t* masks_dev, int n, int min_area,
-                                        float* probs_host, void* stream) {
-    if (!c) return SABER_ERR_INVALID;
+static void cls_launch_bbox(const ClsByteMasks& m, int n, int H, int W, int* bbox, hipStream_t s) {
+    hipLaunchKernelGGL(cls_bbox_kernel, dim3(H, n), dim3(256), 0, s, m.p, H, W, bbox);
+}
+static void cls_launch_bbox(const ClsBitMasks& m, int n, int H, int W, int* bbox, hipStream_t s) {
+    hipLaunchKernelGGL(cls_bbox_bits_kernel, dim3((H + 3) / 4, n), dim3(256), 0, s, m, H, W, bbox);
+}
+
+// Predictor.predict on the n masks `masks` addresses (n >= 1, arguments checked by the C-ABI entry): everything but the two mask reads
+// is shared by the uint8 and the bit-packed route
+template <class Masks>
+static int cls_predict(saber_classifier* c, const float* image_dev, int H, int W, const Masks& masks, int n, int min_area, float* probs_host,
+                       hipStream_t s) {
     saber_engine* e = c->e;
-    if (!c->finalized) return eng_fail(e, SABER_ERR_STATE, "classifier_predict: classifier not finalized");
-    if (n < 0 || H <= 0 || W <= 0 || (n > 0 && (!image_dev || !masks_dev || !probs_host))) return eng_fail(e, SABER_ERR_INVALID, "classifier_predict: bad argument");
-    if (n == 0) return SABER_OK;
-    ENG_DEVICE(e);
-    hipStream_t s = (hipStream_t)stream;
     const int nc = c->num_classes;
     std::fill(probs_host, probs_host + (size_t)n * nc, 0.0f);
     if (c->cap_n < (size_t)n) {
@@ -413,14 +451,14 @@ extern "C" int saber_classifier_predict(saber_classifier* c, const float* image_
     ENG_HIP(e, hipMemsetAsync(c->areas, 0, sizeof(int) * n, s));
     hipLaunchKernelGGL(cls_sums_kernel, dim3(256), dim3(256), 0, s, image_dev, (int64_t)H * W, c->sums);
     hipLaunchKernelGGL(cls_bbox_init_kernel, dim3((n + 255) / 256), dim3(256), 0, s, c->bbox, n, H, W);
-    hipLaunchKernelGGL(cls_bbox_kernel, dim3(H, n), dim3(256), 0, s, masks_dev, H, W, c->bbox);
+    cls_launch_bbox(masks, n, H, W, c->bbox, s);
     std::vector<int> bb((size_t)4 * n), boxes((size_t)4 * n), areas(n);
     ENG_HIP(e, hipMemcpyAsync(bb.data(), c->bbox, sizeof(int) * 4 * n, hipMemcpyDeviceToHost, s));
     ENG_HIP(e, hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i) cls_crop_box(&bb[4 * i], H, W, &boxes[4 * i]);
     // 2. crops + the area filter of Predictor.preprocess (on the resized mask)
     ENG_HIP(e, hipMemcpyAsync(c->boxes, boxes.data(), sizeof(int) * 4 * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(cls_crop_kernel, dim3(CROP_PIX / 256, n), dim3(256), 0, s, image_dev, masks_dev, H, W, c->boxes, c->sums, (double)H * W, c->crops, c->cmask, c->areas);
+    hipLaunchKernelGGL(cls_crop_kernel<Masks>, dim3(CROP_PIX / 256, n), dim3(256), 0, s, image_dev, masks, H, W, c->boxes, c->sums, (double)H * W, c->crops, c->cmask, c->areas);
     ENG_HIP(e, hipMemcpyAsync(areas.data(), c->areas, sizeof(int) * n, hipMemcpyDeviceToHost, s));
     ENG_HIP(e, hipStreamSynchronize(s));
     std::vector<int> valid;
@@ -443,6 +481,36 @@ extern "C" int saber_classifier_predict(saber_classifier* c, const float* image_
     }
     ENG_HIP(e, hipGetLastError());
     return SABER_OK;
+}
+
+extern "C" int saber_classifier_predict(saber_classifier* c, const float* image_dev, int H, int W, const uint8_t* masks_dev, int n, int min_area,
+                                        float* probs_host, void* stream) {
+    if (!c) return SABER_ERR_INVALID;
+    saber_engine* e = c->e;
+    if (!c->finalized) return eng_fail(e, SABER_ERR_STATE, "classifier_predict: classifier not finalized");
+    if (n < 0 || H <= 0 || W <= 0 || (n > 0 && (!image_dev || !masks_dev || !probs_host))) return eng_fail(e, SABER_ERR_INVALID, "classifier_predict: bad argument");
+    if (n == 0) return SABER_OK;
+    ENG_DEVICE(e);
+    return cls_predict(c, image_dev, H, W, ClsByteMasks{masks_dev, H, W}, n, min_area, probs_host, (hipStream_t)stream);
+}
+
+// The same on rows rows_host[0..k) of the mask generator's bit-packed stack: no (k,H,W) uint8 stack exists on this route
+extern "C" int saber_classifier_predict_bits(saber_classifier* c, const float* image_dev, int H, int W, const uint32_t* bits_dev, int n_rows,
+                                             const int* rows_host, int k, int min_area, float* probs_host, void* stream) {
+    if (!c) return SABER_ERR_INVALID;
+    saber_engine* e = c->e;
+    if (!c->finalized) return eng_fail(e, SABER_ERR_STATE, "classifier_predict_bits: classifier not finalized");
+    if (k < 0 || n_rows < 0 || H <= 0 || W <= 0 || (k > 0 && (!image_dev || !bits_dev || !rows_host || !probs_host)))
+        return eng_fail(e, SABER_ERR_INVALID, "classifier_predict_bits: bad argument");
+    for (int i = 0; i < k; ++i)
+        if (rows_host[i] < 0 || rows_host[i] >= n_rows)
+            return eng_fail(e, SABER_ERR_INVALID, "classifier_predict_bits: row " + std::to_string(rows_host[i]) + " is outside the stack of " + std::to_string(n_rows));
+    if (k == 0) return SABER_OK;
+    ENG_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (c->cap_rows < (size_t)k) { TRY(eng_regrow(e, &c->rows, (size_t)k, s)); c->cap_rows = k; }
+    ENG_HIP(e, hipMemcpyAsync(c->rows, rows_host, sizeof(int) * k, hipMemcpyHostToDevice, s));
+    return cls_predict(c, image_dev, H, W, ClsBitMasks{bits_dev, c->rows, H, (W + 31) / 32}, k, min_area, probs_host, s);
 }
 
 // The head alone on the embeddings the engine currently holds in slots 0..k-1 (saber_encode / saber_set_embed_tokens) with caller-provided

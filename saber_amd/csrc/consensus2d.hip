@@ -15,7 +15,9 @@
 //
 // Kernels (union-find with min-index roots as in cc3d.hip: a component's root IS its first pixel in raster order):
 //   cs_accum    one wave per 256-pixel segment of a row: cm, count, avg; every foreground pixel starts as a child of the first pixel
-//               of its x-run within the segment
+//               of its x-run within the segment.  Two forms of the mask read, one body: a (n,H,W) uint8 stack, or rows of the mask
+//               generator's bit-packed (n,H,W32) stack (saber_consensus_components_bits: a lane tests its bit of the word its half of
+//               the 64-pixel chunk shares, an eighth of the bytes); the arithmetic above is the same statements in both
 //   cs_merge    per pixel, the centre neighbour of the row above only (4-connectivity), and only at the first column a run shares
 //               with the run above it; the left neighbour at a segment's first pixel
 //   cs_flatten  parent <- root; a wave covers 64 consecutive pixels, so the ballot of "is a root" IS one 64-bit word of the root bitmap
@@ -28,7 +30,9 @@
 //               scan sums avg over each x-run in a fixed order and a run that crosses 64-pixel chunks is carried along: one table
 //               update (area, box, fp64 sum) per run and segment, combined per block of 16 rows in LDS before it goes to global memory.  Rows past the caller's capacity are dropped on the device, so the host never has to know
 //               K before the last launch.
-// Host synchronisations per call: 1 (the end of the call, which brings K).
+//   cs_paint    saber_relabel_plane: plane[p] = lut[labels[p]], the classified slice's paint (components are disjoint, so painting the
+//               area-sorted survivors one after the other is a table look-up)
+// Host synchronisations per call: 1 (the end of the call, which brings K); saber_relabel_plane: none.
 #include <algorithm>
 #include <string>
 
@@ -67,7 +71,11 @@ __device__ __forceinline__ void cs_unite(uint32_t* lab, uint32_t a, uint32_t b) 
 // segment's first pixel; cs_merge joins them across the seam.
 #define CS_CPL 4
 #define CS_SEG (64 * CS_CPL)
-__global__ __launch_bounds__(256) void cs_accum_kernel(const uint8_t* __restrict__ masks, size_t hw, const int* __restrict__ sel,
+// BITS: `masks` is a bit-packed stack (bit b of word w of a row = pixel 32w+b, W32 words per row, `stride` words per mask) instead of
+// a uint8 one (`stride` = H W bytes per mask).  A segment starts at a multiple of 256 pixels and a chunk at a multiple of 64, so lanes
+// 0..31 of a chunk share one word and lanes 32..63 the next; a pixel inside the row (in[i]) has its word inside the row.
+template <bool BITS>
+__global__ __launch_bounds__(256) void cs_accum_kernel(const void* __restrict__ masks, size_t stride, int W32, const int* __restrict__ sel,
                                                        const float* __restrict__ conf, int k, int W, int nseg, int64_t pieces, double* __restrict__ avg,
                                                        uint32_t* __restrict__ lab) {
     const int lane = threadIdx.x & 63;
@@ -82,14 +90,27 @@ __global__ __launch_bounds__(256) void cs_accum_kernel(const uint8_t* __restrict
         bool in[CS_CPL];
 #pragma unroll
         for (int i = 0; i < CS_CPL; ++i) { cm[i] = 0.0f; cnt[i] = 0; in[i] = xs + 64 * i + lane < W; }
-        const uint8_t* p = masks + base + xs + lane;
+        if (BITS) {
+            const uint32_t* p = (const uint32_t*)masks + piece / nseg * W32 + (xs >> 5) + (lane >> 5);
+            const int bit = lane & 31;
 #pragma unroll 2
-        for (int j = 0; j < k; ++j) {
-            const uint8_t* q = p + (size_t)sel[j] * hw;
-            const float c = conf[j];
+            for (int j = 0; j < k; ++j) {
+                const uint32_t* q = p + (size_t)sel[j] * stride;
+                const float c = conf[j];
 #pragma unroll
-            for (int i = 0; i < CS_CPL; ++i)
-                if (in[i] && q[64 * i]) { cm[i] = __fadd_rn(cm[i], c); ++cnt[i]; }
+                for (int i = 0; i < CS_CPL; ++i)
+                    if (in[i] && ((q[2 * i] >> bit) & 1u)) { cm[i] = __fadd_rn(cm[i], c); ++cnt[i]; }
+            }
+        } else {
+            const uint8_t* p = (const uint8_t*)masks + base + xs + lane;
+#pragma unroll 2
+            for (int j = 0; j < k; ++j) {
+                const uint8_t* q = p + (size_t)sel[j] * stride;
+                const float c = conf[j];
+#pragma unroll
+                for (int i = 0; i < CS_CPL; ++i)
+                    if (in[i] && q[64 * i]) { cm[i] = __fadd_rn(cm[i], c); ++cnt[i]; }
+            }
         }
 #pragma unroll
         for (int i = 0; i < CS_CPL; ++i) {
@@ -311,25 +332,35 @@ __global__ __launch_bounds__(64 * CS_STAT_ROWS) void cs_stats_kernel(const int32
     }
 }
 
+// plane[p] = lut[labels[p]] (lut[0] = 0: background); a label past the table paints nothing
+__global__ __launch_bounds__(256) void cs_paint_kernel(const int32_t* __restrict__ labels, int64_t n, const uint16_t* __restrict__ lut, int L,
+                                                       uint16_t* __restrict__ plane) {
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
+        const int32_t l = labels[v];
+        plane[v] = (uint32_t)l < (uint32_t)L ? lut[l] : (uint16_t)0;
+    }
+}
+
 namespace {
 inline size_t cs_align(size_t b) { return (b + 255) & ~(size_t)255; }
 inline unsigned cs_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
 }  // namespace
 
-extern "C" int saber_consensus_components(saber_engine* e, const uint8_t* masks_dev, int n, int H, int W, const int* select_host,
-                                          const float* conf_host, int k, int capacity, int32_t* labels_out_dev, saber_consensus_row* table_out_dev,
-                                          int* out_n_components, void* stream) {
+// both entries: `bits` says which of the two stacks masks_dev is; `who` names the entry in the error strings
+static int cs_components(saber_engine* e, const std::string& who, const void* masks_dev, bool bits, int n, int H, int W, const int* select_host,
+                         const float* conf_host, int k, int capacity, int32_t* labels_out_dev, saber_consensus_row* table_out_dev,
+                         int* out_n_components, void* stream) {
     if (!e) return SABER_ERR_INVALID;
     if (out_n_components) *out_n_components = 0;
     if (!masks_dev || !select_host || !conf_host || !labels_out_dev || capacity < 0 || (capacity > 0 && !table_out_dev))
-        return eng_fail(e, SABER_ERR_INVALID, "consensus_components: bad argument");
-    if (n < 1 || H < 1 || W < 1) return eng_fail(e, SABER_ERR_INVALID, "consensus_components: n, H and W must be at least 1");
+        return eng_fail(e, SABER_ERR_INVALID, who + ": bad argument");
+    if (n < 1 || H < 1 || W < 1) return eng_fail(e, SABER_ERR_INVALID, who + ": n, H and W must be at least 1");
     const int64_t npx = (int64_t)H * W;
-    if (npx >= (int64_t)0x7fffffff) return eng_fail(e, SABER_ERR_INVALID, "consensus_components: images of 2^31 pixels or more are not supported");
-    if (k < 1 || k > n) return eng_fail(e, SABER_ERR_INVALID, "consensus_components: the selection must hold 1..n masks, got " + std::to_string(k));
+    if (npx >= (int64_t)0x7fffffff) return eng_fail(e, SABER_ERR_INVALID, who + ": images of 2^31 pixels or more are not supported");
+    if (k < 1 || k > n) return eng_fail(e, SABER_ERR_INVALID, who + ": the selection must hold 1..n masks, got " + std::to_string(k));
     for (int j = 0; j < k; ++j)
         if (select_host[j] < 0 || select_host[j] >= n)
-            return eng_fail(e, SABER_ERR_INVALID, "consensus_components: selected index " + std::to_string(select_host[j]) + " is outside the stack of " + std::to_string(n));
+            return eng_fail(e, SABER_ERR_INVALID, who + ": selected index " + std::to_string(select_host[j]) + " is outside the stack of " + std::to_string(n));
     hipStream_t s = (hipStream_t)stream;
     ENG_DEVICE(e);
     const int64_t nw = (npx + 63) / 64;
@@ -365,7 +396,13 @@ extern "C" int saber_consensus_components(saber_engine* e, const uint8_t* masks_
     const int nseg = (W + CS_SEG - 1) / CS_SEG;
     const int64_t pieces = (int64_t)H * nseg;
     const unsigned piece_blocks = (unsigned)((pieces + 3) / 4), px_blocks = cs_blocks(npx);
-    hipLaunchKernelGGL(cs_accum_kernel, dim3(piece_blocks), dim3(256), 0, s, masks_dev, (size_t)npx, (const int*)sel, (const float*)conf, k, W, nseg, pieces, avg, lab);
+    const int W32 = (W + 31) / 32;
+    if (bits)
+        hipLaunchKernelGGL(cs_accum_kernel<true>, dim3(piece_blocks), dim3(256), 0, s, masks_dev, (size_t)H * W32, W32, (const int*)sel, (const float*)conf, k, W, nseg,
+                           pieces, avg, lab);
+    else
+        hipLaunchKernelGGL(cs_accum_kernel<false>, dim3(piece_blocks), dim3(256), 0, s, masks_dev, (size_t)npx, W32, (const int*)sel, (const float*)conf, k, W, nseg,
+                           pieces, avg, lab);
     if (H > 1 || nseg > 1) hipLaunchKernelGGL(cs_merge_kernel, dim3(px_blocks), dim3(256), 0, s, lab, W, npx);
     hipLaunchKernelGGL(cs_flatten_kernel, dim3(cs_blocks(nw * 64)), dim3(256), 0, s, lab, npx, nw, bitmap, groups);
     hipLaunchKernelGGL(cs_rank_groups_kernel, dim3(1), dim3(1024), 0, s, groups, ng, counters);
@@ -381,7 +418,33 @@ extern "C" int saber_consensus_components(saber_engine* e, const uint8_t* masks_
     ENG_HIP(e, hipStreamSynchronize(s));                        // the call's one synchronisation
     if (out_n_components) *out_n_components = (int)K;
     if ((int64_t)K > capacity)
-        return eng_fail(e, SABER_ERR_CAPACITY, "consensus_components: the union has " + std::to_string(K) + " components, the table has room for " +
+        return eng_fail(e, SABER_ERR_CAPACITY, who + ": the union has " + std::to_string(K) + " components, the table has room for " +
                                                    std::to_string(capacity));
+    return SABER_OK;
+}
+
+extern "C" int saber_consensus_components(saber_engine* e, const uint8_t* masks_dev, int n, int H, int W, const int* select_host,
+                                          const float* conf_host, int k, int capacity, int32_t* labels_out_dev, saber_consensus_row* table_out_dev,
+                                          int* out_n_components, void* stream) {
+    return cs_components(e, "consensus_components", masks_dev, false, n, H, W, select_host, conf_host, k, capacity, labels_out_dev, table_out_dev,
+                         out_n_components, stream);
+}
+
+extern "C" int saber_consensus_components_bits(saber_engine* e, const uint32_t* bits_dev, int n_rows, int H, int W, const int* select_host,
+                                               const float* conf_host, int k, int capacity, int32_t* labels_out_dev, saber_consensus_row* table_out_dev,
+                                               int* out_n_components, void* stream) {
+    return cs_components(e, "consensus_components_bits", bits_dev, true, n_rows, H, W, select_host, conf_host, k, capacity, labels_out_dev, table_out_dev,
+                         out_n_components, stream);
+}
+
+extern "C" int saber_relabel_plane(saber_engine* e, const int32_t* labels_dev, int H, int W, const uint16_t* lut_dev, int lut_len, uint16_t* plane_dev,
+                                   void* stream) {
+    if (!e) return SABER_ERR_INVALID;
+    if (!labels_dev || !lut_dev || !plane_dev || H < 1 || W < 1 || lut_len < 1) return eng_fail(e, SABER_ERR_INVALID, "relabel_plane: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ENG_DEVICE(e);
+    const int64_t npx = (int64_t)H * W;
+    hipLaunchKernelGGL(cs_paint_kernel, dim3(cs_blocks(npx)), dim3(256), 0, s, labels_dev, npx, lut_dev, lut_len, plane_dev);
+    ENG_HIP(e, hipGetLastError());
     return SABER_OK;
 }

@@ -365,17 +365,20 @@ class Engine:
         if sel.size == 0 or sel.size > n or sel.min() < 0 or sel.max() >= n or n == 0 or H == 0 or W == 0 or H * W >= 2 ** 31 - 1:
             raise ValueError(f"consensus_components: a selection of 1..n rows of a non-empty (n,H,W) stack with H W < 2^31 is needed, got "
                              f"{sel.size} of {tuple(masks_u8.shape)}")
+        return self._consensus_run(self.lib.saber_consensus_components, masks_u8, n, H, W, sel, cf, capacity)
+
+    def _consensus_run(self, entry, stack: torch.Tensor, n: int, H: int, W: int, sel: np.ndarray, cf: np.ndarray, capacity: Optional[int]):
+        """the capacity protocol and the table download both consensus entries share (stack: the uint8 or the bit-packed tensor)"""
         sel = sel.astype(np.int32)
         if capacity is None:
             capacity = min((H * W + 1) // 2, 65536)
-        labels = torch.empty((H, W), dtype=torch.int32, device=masks_u8.device)
+        labels = torch.empty((H, W), dtype=torch.int32, device=stack.device)
         k = C.c_int(0)
         with torch.cuda.device(self.device):
             while True:
-                table = torch.empty((max(int(capacity), 1), self.CONSENSUS_ROW.itemsize), dtype=torch.uint8, device=masks_u8.device)
-                st = self.lib.saber_consensus_components(self.h, _ptr(masks_u8), n, H, W, sel.ctypes.data_as(C.POINTER(C.c_int)),
-                                                         cf.ctypes.data_as(C.POINTER(C.c_float)), int(sel.size), int(capacity), _ptr(labels),
-                                                         _ptr(table), C.byref(k), _stream())
+                table = torch.empty((max(int(capacity), 1), self.CONSENSUS_ROW.itemsize), dtype=torch.uint8, device=stack.device)
+                st = entry(self.h, _ptr(stack), n, H, W, sel.ctypes.data_as(C.POINTER(C.c_int)), cf.ctypes.data_as(C.POINTER(C.c_float)),
+                           int(sel.size), int(capacity), _ptr(labels), _ptr(table), C.byref(k), _stream())
                 if st == _lib.SABER_ERR_CAPACITY and k.value > capacity:
                     capacity = k.value
                     continue
@@ -385,6 +388,46 @@ class Engine:
         out = {name: rows[name].astype(np.int64) for name in ("area", "x_min", "y_min", "x_max", "y_max")}
         out["score"] = rows["avg_sum"] / np.maximum(rows["area"], 1).astype(np.float64)
         return labels, out
+
+    def consensus_components_bits(self, bits: torch.Tensor, W: int, select: Sequence[int], conf, capacity: Optional[int] = None):
+        """consensus_components on rows of the mask generator's bit-packed stack (include/saber_amd.h: saber_consensus_components_bits).
+        bits: (n,H,W32) int32 / uint32 device tensor as amg_generate returns it (bit b of word w = pixel 32w+b), W: the image width;
+        select, conf, capacity and the returned (labels, table) as in consensus_components.  No uint8 stack is made."""
+        if not isinstance(bits, torch.Tensor) or not bits.is_cuda:
+            raise ValueError("consensus_components_bits: the mask stack must be a device tensor")
+        if bits.dtype not in (torch.int32, torch.uint32) or bits.dim() != 3 or bits.shape[2] != (int(W) + 31) // 32:
+            raise ValueError(f"consensus_components_bits: the mask stack must be (n,H,ceil(W/32)) int32 for W = {W}, got {tuple(bits.shape)} {bits.dtype}")
+        if bits.device != self.device:
+            raise ValueError(f"consensus_components_bits: the mask stack is on {bits.device}, the engine on {self.device}")
+        bits = bits.contiguous()
+        sel = np.ascontiguousarray(np.asarray(select, dtype=np.int64).reshape(-1))
+        cf = np.ascontiguousarray(np.asarray(conf).reshape(-1).astype(np.float32))
+        n, H, W = int(bits.shape[0]), int(bits.shape[1]), int(W)
+        if sel.size != cf.size:
+            raise ValueError(f"consensus_components_bits: {sel.size} selected masks, {cf.size} confidences")
+        if sel.size == 0 or sel.size > n or sel.min() < 0 or sel.max() >= n or n == 0 or H == 0 or W == 0 or H * W >= 2 ** 31 - 1:
+            raise ValueError(f"consensus_components_bits: a selection of 1..n rows of a non-empty (n,H,W32) stack with H W < 2^31 is needed, got "
+                             f"{sel.size} of {tuple(bits.shape)}")
+        return self._consensus_run(self.lib.saber_consensus_components_bits, bits, n, H, W, sel, cf, capacity)
+
+    def relabel_plane(self, labels: torch.Tensor, lut) -> torch.Tensor:
+        """plane[p] = lut[labels[p]] (include/saber_amd.h: saber_relabel_plane).  labels: (H,W) int32 device tensor (a consensus call's
+        label plane), lut: K + 1 uint16 values, lut[0] = 0, as a numpy array (uploaded here) or a device tensor of int16 / uint16.
+        Returns the (H,W) uint16 device plane; no host synchronisation."""
+        if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.int32 or labels.dim() != 2:
+            raise ValueError("relabel_plane: labels must be an (H,W) int32 device tensor")
+        if labels.device != self.device:
+            raise ValueError(f"relabel_plane: the labels are on {labels.device}, the engine on {self.device}")
+        if not isinstance(lut, torch.Tensor):
+            lut = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.uint16).reshape(-1).view(np.int16)).to(self.device)
+        if lut.dtype not in (torch.int16, torch.uint16) or lut.dim() != 1 or lut.numel() < 1 or lut.device != self.device:
+            raise ValueError("relabel_plane: lut must hold at least one uint16 value on the engine's device")
+        labels, lut = labels.contiguous(), lut.contiguous()
+        H, W = labels.shape
+        plane = torch.empty((H, W), dtype=torch.uint16, device=self.device)
+        if H * W:
+            self._check(self.lib.saber_relabel_plane(self.h, _ptr(labels), H, W, _ptr(lut), int(lut.numel()), _ptr(plane), _stream()))
+        return plane
 
     def set_precision(self, precision: str):
         """Switch between the handle's 16-bit production arithmetic ("bf16" or "fp16": whichever its weights were converted to) and the

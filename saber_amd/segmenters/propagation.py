@@ -140,24 +140,34 @@ class propagationSegmenter(saber3D):
         """Same result as slice_by_slice, computed with device-resident masks and z-sharded over the ranks of the
         default torch.distributed process group (single process: all slices).  smooth_scale=0.05 appends the adaptive Gaussian
         smoothing segment_tomogram_core applies to the result (inference_core.py:68-74), still on the device (uint8 output)."""
+        from saber_amd.adapters.sam2.automask import get_replica
         from saber_amd.segmenters.slice_driver import segment_slice_to_plane, segment_volume_sharded
         gen = self.adapter._generator()
         eng, params = gen.base_generator.engine, gen.base_generator.params
         engines = [eng]
         if handles_per_gpu > 1:
             # replicas of the PRIMARY engine's model (the adapter's own `cfg` field may name another trunk)
-            from saber_amd.adapters.sam2.automask import get_replica
             engines += [get_replica(eng, r) for r in range(1, handles_per_gpu)]
 
-        def make(engine):
+        # classifier filter (saber2D._apply_classifier): one Predictor per thread, on an engine handle of its own.  When the classifier's
+        # backbone IS the AMG engine, thread w's generator and classifier share replica w and run one after the other on that thread's
+        # stream: the generator's masks and scalars are final (its call has synchronised) before the classifier's crops overwrite the
+        # encoder slots.  self.batchsize lands in the component area filter, as on the host route (base.py, _apply_classifier).
+        classifiers = [None] * len(engines)
+        if self.classifier is not None:
+            classifiers = [self.classifier if w == 0 else self.classifier.replica(get_replica(self.classifier.engine, w))
+                           for w in range(len(engines))]
+
+        def make(engine, classifier):
             def one(z):
                 sl = volume[z]
                 if isinstance(sl, np.ndarray):
                     sl = torch.from_numpy(np.ascontiguousarray(sl if sl.dtype == np.uint16 else sl.astype(np.float32))).to(engine.device)
                 plane, _ = segment_slice_to_plane(engine, sl, params, min_mask_area=self.min_mask_area,
-                                                  remove_repeating_masks=self.remove_repeating_masks, max_masks=gen.base_generator.max_masks)
+                                                  remove_repeating_masks=self.remove_repeating_masks, max_masks=gen.base_generator.max_masks,
+                                                  classifier=classifier, target_class=1, classifier_min_area=self.batchsize)
                 return plane
             return one
 
-        one = [make(e) for e in engines]
+        one = [make(e, c) for e, c in zip(engines, classifiers)]
         return segment_volume_sharded(volume, one, stitch=stitch, engine=eng, smooth_scale=smooth_scale)   # 3-D CC (+ smoothing) on the device

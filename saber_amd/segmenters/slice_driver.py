@@ -10,6 +10,12 @@
     _apply_classifier (base.py:159-176): area >= min_mask_area, remove_duplicate_masks, ascending-area sort
     paint idx+1 in list order (later masks overwrite), np.maximum with the zero plane (:185-188)
 
+With a classifier (the segmenter's config carries one) _apply_classifier instead hands the surviving masks, unsorted, to
+filters.apply_classifier (saber/filters/masks.py:8-62): class probabilities of every mask, the masks of the target class merged by
+the consensus resolution, components below the area threshold dropped, ascending area.  Here the masks stay the generator's bit-packed
+rows from the classifier's crop kernel to the painted plane (Predictor.batch_predict_bits, Engine.consensus_components_bits,
+Engine.relabel_plane); the host decides from per-mask and per-component scalars only.
+
 `segment_volume_sharded` is the multi-GPU form: rank r owns a contiguous z-chunk, planes are all-gathered
 (RCCL when the process group is NCCL, gloo in the CPU tests) and rank 0 (or every rank) stitches with separate_masks.
 """
@@ -21,32 +27,85 @@ import torch
 from . import utils
 
 
-def select_and_order(meta, inter: np.ndarray, min_mask_area: int, remove_repeating_masks: bool = True):
-    """Host decisions of saber2D._apply_classifier (classifier=None) on per-mask scalars.
-    Returns indices into `meta` in final (paint) order."""
+def select_masks(meta, inter: np.ndarray, min_mask_area: int, remove_repeating_masks: bool = True):
+    """The area filter and duplicate removal of saber2D._apply_classifier on per-mask scalars.  Returns indices into `meta` in list
+    (generator) order."""
     idx = [i for i, m in enumerate(meta) if m.area >= min_mask_area]
     if remove_repeating_masks and idx:
         sub = inter[np.ix_(idx, idx)]
         keep = utils.duplicate_groups_from_counts([meta[i].area for i in idx], sub, [meta[i].stability_score for i in idx])
         idx = [idx[k] for k in keep]
+    return idx
+
+
+def select_and_order(meta, inter: np.ndarray, min_mask_area: int, remove_repeating_masks: bool = True):
+    """Host decisions of saber2D._apply_classifier (classifier=None) on per-mask scalars.
+    Returns indices into `meta` in final (paint) order."""
+    idx = select_masks(meta, inter, min_mask_area, remove_repeating_masks)
     idx.sort(key=lambda i: meta[i].area)  # sorted() is stable: ties keep AMG order
     return idx
 
 
+def classified_paint_lut(areas, min_area: int) -> np.ndarray:
+    """The paint values of a classified slice as a table over the consensus components: uint16[K + 1], entry 0 (background) = 0,
+    entry i + 1 = the value component i is painted with.  convert_predictions_to_masks keeps the components with area >= min_area and
+    sorts them by ascending area (sorted() is stable: ties keep label order); slice_by_slice paints position + 1 in that order.  The
+    components are disjoint, so that paint loop is this look-up.  Raises when more than 65535 components survive (uint16 plane)."""
+    a = np.asarray(areas, dtype=np.int64).reshape(-1)
+    keep = np.flatnonzero(a >= min_area)
+    if keep.size > 65535:
+        raise ValueError(f"classified_paint_lut: {keep.size} components survive the area filter, a uint16 plane holds 65535")
+    order = keep[np.argsort(a[keep], kind="stable")]
+    lut = np.zeros(a.size + 1, dtype=np.uint16)
+    lut[order + 1] = np.arange(1, order.size + 1, dtype=np.uint16)
+    return lut
+
+
 def segment_slice_to_plane(engine, raw_slice: torch.Tensor, params, min_mask_area: int = 50,
-                           remove_repeating_masks: bool = True, max_masks: int = 2048) -> Tuple[torch.Tensor, int]:
+                           remove_repeating_masks: bool = True, max_masks: int = 2048, classifier=None, target_class: int = 1,
+                           classifier_min_area: int = 32) -> Tuple[torch.Tensor, int]:
     """raw_slice: (H,W) uint16/float32 device tensor.  Returns ((H,W) uint16 label plane on device, n masks).
     max_masks is the same capacity the adapter path uses (EngineMaskGenerator.max_masks); a denser slice is retried once with the
-    count the engine reports instead of failing the volume."""
+    count the engine reports instead of failing the volume.
+    classifier (a Predictor on an engine handle no other thread uses; None = no classifier filter): the slice takes the classifier
+    branch of _apply_classifier for target_class > 0, with classifier_min_area as the component area filter; n masks is then the number
+    of painted components.  The semantic branch (target_class <= 0) is not a slice-loop result: ValueError."""
+    if classifier is not None and (target_class is None or target_class <= 0):
+        raise ValueError(f"segment_slice_to_plane: the classifier route needs target_class > 0, got {target_class} (the semantic branch is "
+                         "not part of the slice loop)")
     H, W = raw_slice.shape
     img = engine.prepare(raw_slice)
     bits, meta = engine.amg_generate(img, params, max_masks=max_masks)
     if len(meta) == 0:
         return torch.zeros((H, W), dtype=torch.uint16, device=raw_slice.device), 0
     inter = engine.pair_intersections(bits, H, W).cpu().numpy() if remove_repeating_masks else None
+    if classifier is not None:
+        return _classified_plane(engine, raw_slice, bits, select_masks(meta, inter, min_mask_area, remove_repeating_masks), classifier,
+                                 target_class, classifier_min_area)
     order = select_and_order(meta, inter, min_mask_area, remove_repeating_masks)
     plane = engine.label_plane(bits, order, H, W)
     return plane, len(order)
+
+
+def _classified_plane(engine, raw_slice: torch.Tensor, bits: torch.Tensor, rows, classifier, target_class: int, min_area: int):
+    """filters.apply_classifier + the paint loop on bit-packed rows.  rows: the masks that reach the classifier, in list order.
+    The classifier sees the raw slice as float32 (the host route hands it volume[z]); its group size is batch_predict's default."""
+    H, W = raw_slice.shape
+    empty = lambda: (torch.zeros((H, W), dtype=torch.uint16, device=raw_slice.device), 0)
+    if len(rows) == 0:
+        return empty()
+    gray = raw_slice
+    if gray.dtype == torch.uint16:                  # exact; through int32, which every torch build converts
+        gray = gray.view(torch.int16).to(torch.int32).bitwise_and_(0xFFFF)
+    gray = gray.to(torch.float32)
+    predictions = classifier.batch_predict_bits(gray, bits, rows, W)
+    predicted = np.argmax(predictions, axis=1)
+    keep = [j for j, p in enumerate(predicted) if p == target_class]
+    if not keep:
+        return empty()
+    labels, table = engine.consensus_components_bits(bits, W, [rows[j] for j in keep], predictions[keep, target_class])
+    lut = classified_paint_lut(table["area"], min_area)
+    return engine.relabel_plane(labels, lut), int(np.count_nonzero(lut))
 
 
 def shard_bounds(Z: int, world: int, rank: int) -> Tuple[int, int]:
