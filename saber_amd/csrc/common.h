@@ -160,6 +160,31 @@ __device__ __forceinline__ float wave_sum(float v) { return xor32_sum(xor16_sum(
 __device__ __forceinline__ float wave_max(float v) { return xor32_max(xor16_max(row16_max(v))); }
 __device__ __forceinline__ float wave_min(float v) { return xor32_min(xor16_min(row16_min(v))); }
 
+// Integer all-reduces over the wave, five __shfl_xor steps, for a kernel that reduces ONE value (or two at its very end).  Where
+// several values are reduced together inside a loop (sm_stats_kernel, ls_moments_kernel) the kernel keeps one ladder over all of
+// them: written as separate calls, the shuffles of a step are no longer issued together and the kernel needs more registers.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
+}
+
+// Inclusive prefix sum over the NT threads of a block (Hillis-Steele in LDS).  On entry thread t has stored its value in part[t]
+// (no barrier needed in between); on return part[t] = part[0] + ... + part[t], visible to every thread.  All NT threads must call it.
+template <int NT>
+__device__ __forceinline__ void block_scan_inclusive(uint32_t* part, int t) {
+    __syncthreads();
+    for (int o = 1; o < NT; o <<= 1) {
+        const uint32_t a = t >= o ? part[t - o] : 0u;
+        __syncthreads();
+        part[t] += a;
+        __syncthreads();
+    }
+}
+
 // Hiera token order used throughout the engine (DESIGN.md "token order"): for the
 // 256x256 stage-0 grid, index bits are [y7 y6 x7 x6][y5 y4 y3 x5 x4 x3][y2 x2][y1 x1][y0 x0].
 // Every attention window of every stage and every 2x2 pooling group is then a contiguous

@@ -13,7 +13,7 @@
 //          the area.  The sum's order differs from numpy's pairwise one (and, with atomics, between calls): both lie within the
 //          any-order bound area * 2^-53 / (1 - area * 2^-53) * sum|avg| of the exact sum.
 //
-// Kernels (union-find with min-index roots as in cc3d.hip: a component's root IS its first pixel in raster order):
+// Kernels (the union-find with min-index roots of ccl.h: a component's root IS its first pixel in raster order):
 //   cs_accum    one wave per 256-pixel segment of a row: cm, count, avg; every foreground pixel starts as a child of the first pixel
 //               of its x-run within the segment.  Two forms of the mask read, one body: a (n,H,W) uint8 stack, or rows of the mask
 //               generator's bit-packed (n,H,W32) stack (saber_consensus_components_bits: a lane tests its bit of the word its half of
@@ -36,34 +36,13 @@
 #include <algorithm>
 #include <string>
 
+#include "ccl.h"
+#include "common.h"
 #include "engine.h"
 
-#define CS_NONE 0xffffffffu
 #define CS_GROUP_SHIFT 10        // bitmap words per group of the two-level rank (1024 words = 65536 pixels)
 
 typedef unsigned long long cs_u64;
-
-__device__ __forceinline__ uint32_t cs_find(uint32_t* lab, uint32_t x) {
-    uint32_t p = lab[x];
-    while (p != x) {
-        const uint32_t g = lab[p];
-        if (g != p) lab[x] = g;      // path halving: only non-root entries are written, roots change by atomicMin alone
-        x = p;
-        p = g;
-    }
-    return x;
-}
-__device__ __forceinline__ void cs_unite(uint32_t* lab, uint32_t a, uint32_t b) {
-    while (true) {
-        a = cs_find(lab, a);
-        b = cs_find(lab, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }      // hang the larger root under the smaller one
-        const uint32_t old = atomicMin(&lab[a], b);
-        if (old == a) return;
-        a = old;                                               // somebody re-parented a meanwhile: continue from there
-    }
-}
 
 // One wave per segment of CS_SEG pixels of a row (a wave per row leaves a 1024-row image with one wave per SIMD, waiting on its own
 // loads).  sel / conf are wave-uniform reads.  A lane owns CS_CPL pixels 64 apart, so a mask costs it CS_CPL independent byte loads and the
@@ -82,7 +61,7 @@ __global__ __launch_bounds__(256) void cs_accum_kernel(const void* __restrict__ 
     const int64_t piece = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (piece >= pieces) return;                               // wave-uniform
     const int64_t base = piece / nseg * W;
-    uint32_t carry = CS_NONE;                                  // start of the run that reaches the previous chunk's last pixel
+    uint32_t carry = CCL_NONE;                                 // start of the run that reaches the previous chunk's last pixel
     {
         const int xs = (int)(piece % nseg) * CS_SEG;
         float cm[CS_CPL];
@@ -118,33 +97,28 @@ __global__ __launch_bounds__(256) void cs_accum_kernel(const void* __restrict__ 
             if (x0 >= W) break;                                // wave-uniform
             const int x = x0 + lane;
             const bool fg = cnt[i] > 0;
-            const cs_u64 mask = __ballot(fg);
-            uint32_t start = CS_NONE;
+            const uint32_t start = ccl_run_start(fg, lane, (uint32_t)(base + x0), carry);
             if (fg) {
-                const cs_u64 below_bg = ~mask & ((1ull << lane) - 1ull);
-                if (below_bg == 0ull) start = carry != CS_NONE ? carry : (uint32_t)(base + x0);
-                else start = (uint32_t)(base + x0 + (64 - __clzll((long long)below_bg)));
                 lab[base + x] = start;
                 avg[base + x] = __ddiv_rn((double)cm[i], (double)cnt[i]);
             } else if (x < W) {
-                lab[base + x] = CS_NONE;
+                lab[base + x] = CCL_NONE;
                 avg[base + x] = 0.0;
             }
-            carry = __shfl(start, 63, 64);                     // CS_NONE when the chunk's last pixel is background / past the row
         }
     }
 }
 
 __global__ __launch_bounds__(256) void cs_merge_kernel(uint32_t* lab, int W, int64_t n) {
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
-        if (lab[v] == CS_NONE) continue;
+        if (lab[v] == CCL_NONE) continue;
         const int x = (int)(v % W);
-        const bool left = x != 0 && lab[v - 1] != CS_NONE;
-        if (left && x % CS_SEG == 0) cs_unite(lab, (uint32_t)v, (uint32_t)(v - 1));      // the seam between two segments of cs_accum
-        if (v < W || lab[v - W] == CS_NONE) continue;
+        const bool left = x != 0 && lab[v - 1] != CCL_NONE;
+        if (left && x % CS_SEG == 0) ccl_unite(lab, (uint32_t)v, (uint32_t)(v - 1));      // the seam between two segments of cs_accum
+        if (v < W || lab[v - W] == CCL_NONE) continue;
         // the run of v and the run above it are joined at the first column they share: x = 0, or one of the two runs begins here
-        if (left && lab[v - W - 1] != CS_NONE) continue;
-        cs_unite(lab, (uint32_t)v, (uint32_t)(v - W));
+        if (left && lab[v - W - 1] != CCL_NONE) continue;
+        ccl_unite(lab, (uint32_t)v, (uint32_t)(v - W));
     }
 }
 
@@ -152,10 +126,10 @@ __global__ __launch_bounds__(256) void cs_flatten_kernel(uint32_t* lab, int64_t 
     const int lane = threadIdx.x & 63;
     for (int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < chunks; c += (int64_t)gridDim.x * 4) {   // wave-uniform
         const int64_t v = c * 64 + lane;
-        uint32_t p = v < n ? lab[v] : CS_NONE;
+        uint32_t p = v < n ? lab[v] : CCL_NONE;
         bool root = false;
-        if (p != CS_NONE) {
-            while (true) { const uint32_t g = lab[p]; if (g == p) break; p = g; }
+        if (p != CCL_NONE) {
+            p = ccl_root(lab, p);
             lab[v] = p;
             root = p == (uint32_t)v;
         }
@@ -176,13 +150,7 @@ __global__ __launch_bounds__(1024) void cs_rank_groups_kernel(uint32_t* __restri
     uint32_t s = 0;
     for (int64_t g = g0; g < g1; ++g) s += groupsum[g];
     part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t a = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += a;
-        __syncthreads();
-    }
+    block_scan_inclusive<1024>(part, t);
     uint32_t run = part[t] - s;
     for (int64_t g = g0; g < g1; ++g) { const uint32_t c = groupsum[g]; groupsum[g] = run; run += c; }
     if (t == 1023) counters[0] = part[1023];
@@ -198,13 +166,7 @@ __global__ __launch_bounds__(256) void cs_rank_words_kernel(const cs_u64* __rest
 #pragma unroll
     for (int i = 0; i < 4; ++i) { c[i] = w0 + i < nw ? (uint32_t)__popcll(bitmap[w0 + i]) : 0u; s += c[i]; }
     part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const uint32_t a = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += a;
-        __syncthreads();
-    }
+    block_scan_inclusive<256>(part, t);
     uint32_t run = groupbase[blockIdx.x] + part[t] - s;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -218,7 +180,7 @@ __global__ __launch_bounds__(256) void cs_relabel_kernel(uint32_t* lab, int64_t 
     const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
     for (int64_t v = t0; v < n; v += stride) {
         const uint32_t r = lab[v];                             // a pixel reads and writes its own entry only
-        lab[v] = r == CS_NONE ? 0u : 1u + rankbase[r >> 6] + (uint32_t)__popcll(bitmap[r >> 6] & ((1ull << (r & 63)) - 1ull));
+        lab[v] = r == CCL_NONE ? 0u : 1u + rankbase[r >> 6] + (uint32_t)__popcll(bitmap[r >> 6] & ((1ull << (r & 63)) - 1ull));
     }
     const int64_t rows = min((int64_t)counters[0], (int64_t)capacity);
     for (int64_t i = t0; i < rows; i += stride) {
@@ -343,7 +305,6 @@ __global__ __launch_bounds__(256) void cs_paint_kernel(const int32_t* __restrict
 
 namespace {
 inline size_t cs_align(size_t b) { return (b + 255) & ~(size_t)255; }
-inline unsigned cs_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
 }  // namespace
 
 // both entries: `bits` says which of the two stacks masks_dev is; `who` names the entry in the error strings
@@ -395,7 +356,7 @@ static int cs_components(saber_engine* e, const std::string& who, const void* ma
     ENG_HIP(e, hipMemsetAsync(groups, 0, (size_t)ng * 4, s));
     const int nseg = (W + CS_SEG - 1) / CS_SEG;
     const int64_t pieces = (int64_t)H * nseg;
-    const unsigned piece_blocks = (unsigned)((pieces + 3) / 4), px_blocks = cs_blocks(npx);
+    const unsigned piece_blocks = (unsigned)((pieces + 3) / 4), px_blocks = eng_blocks(npx);
     const int W32 = (W + 31) / 32;
     if (bits)
         hipLaunchKernelGGL(cs_accum_kernel<true>, dim3(piece_blocks), dim3(256), 0, s, masks_dev, (size_t)H * W32, W32, (const int*)sel, (const float*)conf, k, W, nseg,
@@ -404,7 +365,7 @@ static int cs_components(saber_engine* e, const std::string& who, const void* ma
         hipLaunchKernelGGL(cs_accum_kernel<false>, dim3(piece_blocks), dim3(256), 0, s, masks_dev, (size_t)npx, W32, (const int*)sel, (const float*)conf, k, W, nseg,
                            pieces, avg, lab);
     if (H > 1 || nseg > 1) hipLaunchKernelGGL(cs_merge_kernel, dim3(px_blocks), dim3(256), 0, s, lab, W, npx);
-    hipLaunchKernelGGL(cs_flatten_kernel, dim3(cs_blocks(nw * 64)), dim3(256), 0, s, lab, npx, nw, bitmap, groups);
+    hipLaunchKernelGGL(cs_flatten_kernel, dim3(eng_blocks(nw * 64)), dim3(256), 0, s, lab, npx, nw, bitmap, groups);
     hipLaunchKernelGGL(cs_rank_groups_kernel, dim3(1), dim3(1024), 0, s, groups, ng, counters);
     hipLaunchKernelGGL(cs_rank_words_kernel, dim3((unsigned)ng), dim3(256), 0, s, (const cs_u64*)bitmap, nw, (const uint32_t*)groups, rankbase);
     hipLaunchKernelGGL(cs_relabel_kernel, dim3(px_blocks), dim3(256), 0, s, lab, npx, (const cs_u64*)bitmap, (const uint32_t*)rankbase,
@@ -444,7 +405,7 @@ extern "C" int saber_relabel_plane(saber_engine* e, const int32_t* labels_dev, i
     hipStream_t s = (hipStream_t)stream;
     ENG_DEVICE(e);
     const int64_t npx = (int64_t)H * W;
-    hipLaunchKernelGGL(cs_paint_kernel, dim3(cs_blocks(npx)), dim3(256), 0, s, labels_dev, npx, lut_dev, lut_len, plane_dev);
+    hipLaunchKernelGGL(cs_paint_kernel, dim3(eng_blocks(npx)), dim3(256), 0, s, labels_dev, npx, lut_dev, lut_len, plane_dev);
     ENG_HIP(e, hipGetLastError());
     return SABER_OK;
 }

@@ -1,6 +1,7 @@
 // Engine state shared by engine.hip (encode / decode) and amg.hip (automatic mask generation).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <set>
@@ -171,6 +172,12 @@ void prof_end(saber_engine* e, hipStream_t s);
 
 int eng_fail(saber_engine* e, int code, const std::string& msg);
 void refine_release(saber_engine* e);       // morph3d.hip: frees refine_state
+// smooth3d.hip: largest label value (atomicMax into *out) and stats[v] = {count, zmin, ymin, xmin, zmax, ymax, xmax, -} of a (Z,H,W)
+// label volume of 1-, 2- or 4-byte unsigned elements; with zflag only the planes z whose zflag[z] is set count.  They only enqueue.
+void label_max(const void* lab, int elem_bytes, const uint8_t* zflag_or_null, int64_t plane, int64_t n, uint32_t* out, hipStream_t s);
+void label_stats(const void* lab, int elem_bytes, const uint8_t* zflag_or_null, int Z, int H, int W, uint32_t* stats, hipStream_t s);
+// blocks of 256 threads for n elements of a grid-stride kernel: at least one, at most cap
+inline unsigned eng_blocks(int64_t n, int64_t cap = 1 << 16) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, cap)); }
 // h[0..2]: the sentinel counters as read from the device; SABER_OK or SABER_ERR_RANGE with a message that names the stage
 int eng_check_finite_counts(saber_engine* e, const unsigned int* h);
 // Binds the calling thread to the engine's device for the duration of one C-ABI call and restores the caller's current device on
@@ -194,6 +201,12 @@ struct DeviceGuard {
     do {                                                                                              \
         hipError_t _st = (call);                                                                      \
         if (_st != hipSuccess) return eng_fail((e), SABER_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); \
+    } while (0)
+// for a function with a local cleanup() (a lambda that frees the call's scratch): run it, then fail as ENG_HIP does
+#define ENG_HIP_CLEANUP(e, call)                                                                      \
+    do {                                                                                              \
+        hipError_t _st = (call);                                                                      \
+        if (_st != hipSuccess) { cleanup(); return eng_fail((e), SABER_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); } \
     } while (0)
 #define ENG_K(e, call)                                                   \
     do {                                                                 \

@@ -13,7 +13,7 @@
 //   ls_moments      one read: 16 uint64 words per label, LS_WORDS below.  A wave owns a 512-voxel piece of a row (z and y fixed), lane l
 //                   holds the voxels l, l + 64, ... (coalesced loads) and sums count, sum d, sum d^2 of the piece-relative offsets d < 512
 //                   of its current label in 32-bit registers.  At the end of the piece the lanes that hold the same label combine (the
-//                   pattern of mo_stats_kernel / sm_stats_kernel); only those three sums and the two x bounds cross lanes.  The ten
+//                   pattern of sm_stats_kernel, smooth3d.hip); only those three sums and the two x bounds cross lanes.  The ten
 //                   sums are those three times z, y, z^2, y^2, zy (64-bit), formed by 16 lanes, one word each, so a table update is one
 //                   128-byte row.  The updates go to a table in LDS keyed by the label's rank (128 direct-mapped slots; a rank that finds
 //                   its slot taken by another goes to global memory directly) and a block covers up to 64 consecutive pieces, so what
@@ -30,6 +30,7 @@
 #include <string>
 #include <type_traits>
 
+#include "common.h"
 #include "engine.h"
 
 #define LS_WORDS 16              // n, Sz, Sy, Sx, Szz, Syy, Sxx, Szy, Szx, Syx, zmin, ymin, xmin, zmax, ymax, xmax
@@ -89,13 +90,7 @@ __global__ __launch_bounds__(1024) void ls_rank_kernel(const uint32_t* __restric
     uint32_t s = 0;
     for (int w = w0; w < w1; ++w) s += (uint32_t)__popc(bitmap[w]);
     part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t a = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += a;
-        __syncthreads();
-    }
+    block_scan_inclusive<1024>(part, t);
     uint32_t run = part[t] - s;
     for (int w = w0; w < w1; ++w) { rankbase[w] = run; run += (uint32_t)__popc(bitmap[w]); }
     if (t == 1023) counters[0] = part[1023];
@@ -268,8 +263,6 @@ __global__ __launch_bounds__(256) void ls_finalize_kernel(const ls_u64* __restri
 
 // ------------------------------------------------------------------------------------------------ host side
 namespace {
-inline unsigned ls_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
-
 template <typename T>
 void ls_launch(const T* lab, int Z, int H, int W, int mode, uint32_t* bitmap, uint32_t* rankbase, ls_u64* mom, hipStream_t s) {
     const int64_t rows = (int64_t)Z * H;
@@ -302,7 +295,7 @@ int ls_run(saber_engine* e, const T* lab, int Z, int H, int W, int capacity, int
     const int nw = (int)(vmax >> 5) + 1;
     ENG_HIP(e, hipMemsetAsync(bitmap, 0, (size_t)nw * 4, s));
     ENG_HIP(e, hipMemsetAsync(counters, 0, 16, s));
-    hipLaunchKernelGGL(ls_presence_kernel<T>, dim3(ls_blocks(n)), dim3(256), 0, s, lab, n, bitmap, counters + 1);
+    hipLaunchKernelGGL(ls_presence_kernel<T>, dim3(eng_blocks(n)), dim3(256), 0, s, lab, n, bitmap, counters + 1);
     hipLaunchKernelGGL(ls_rank_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)bitmap, nw, rankbase, counters);
     ENG_HIP(e, hipGetLastError());
     uint32_t host[2] = {0, 0};
@@ -317,7 +310,7 @@ int ls_run(saber_engine* e, const T* lab, int Z, int H, int W, int capacity, int
                                                    std::to_string(capacity));
     if (!labels_out || !mom || !stats) return eng_fail(e, SABER_ERR_INVALID, "label_statistics: bad argument");
     hipLaunchKernelGGL(ls_labels_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, (const uint32_t*)bitmap, (const uint32_t*)rankbase, nw, labels_out);
-    hipLaunchKernelGGL(ls_init_kernel, dim3(ls_blocks(K * LS_WORDS)), dim3(256), 0, s, mom, K * LS_WORDS);
+    hipLaunchKernelGGL(ls_init_kernel, dim3(eng_blocks(K * LS_WORDS)), dim3(256), 0, s, mom, K * LS_WORDS);
     ls_launch<T>(lab, Z, H, W, mode, bitmap, rankbase, mom, s);
     hipLaunchKernelGGL(ls_finalize_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, (const ls_u64*)mom, (int)K, stats);
     ENG_HIP(e, hipGetLastError());

@@ -13,11 +13,11 @@
 //                         and every offset costs 3 LDS reads + 3 ORs, every k two funnel shifts.  Erosion is the dual with AND; voxels
 //                         outside the volume are 0 for both.  A block owns TY rows x TW words and walks z: a ring of 2r+1 packed
 //                         planes (with a halo of r rows and one word) lives in LDS, each step loads one new plane.
-//   cc6_*                 union-find with min-index roots as in cc3d.hip, 6-connectivity: x-neighbours through the runs of cc_init,
-//                         then (z,y-1,x) and (z-1,y,x).  Two consumers, both without a host round trip: "zero the components below
-//                         min_size" and "keep the largest, the first in raster order on ties" (one 64-bit atomicMax over the roots of
-//                         size << 32 | ~root).
-//   mo_stats              voxel count + bounding box per organelle label (the wave-combining pattern of sm_stats_kernel)
+//   cc6_*                 the union-find with min-index roots of ccl.h, 6-connectivity: x-neighbours through the runs of ccl_init,
+//                         then (z,y-1,x) and (z-1,y,x) in cc6_merge.  Two consumers, both without a host round trip: "zero the
+//                         components below min_size" and "keep the largest, the first in raster order on ties" (one 64-bit atomicMax
+//                         over the roots of size << 32 | ~root).
+//   label_max / _stats    largest label, voxel count + bounding box per organelle label on the planes that hold membrane (smooth3d.hip)
 //   small kernels         edge trim, per-z membrane presence, byte OR / AND, population count, the 3x3x3 organelle boundary of the
 //                         surface test (inside cc6_overlap), scatter into the two label maps, expansion of stored pairs into planes.
 // Host synchronisations of one saber_refine_membranes call: 3 (largest label; per-label statistics; per-organelle flags at the end),
@@ -26,12 +26,13 @@
 #include <cmath>
 #include <vector>
 
+#include "ccl.h"
+#include "common.h"
 #include "engine.h"
 
 #define MO_MAX_R 16
 #define MO_ZC 16                 // output planes per block of mo_ball (the ring is refilled per chunk: 2r planes of halo)
 #define MO_MAX_LABEL (1u << 22)
-#define MO_NONE 0xffffffffu
 #define MO_LDS_LIMIT (150 * 1024)
 
 // ------------------------------------------------------------------------------------------------ pack / unpack
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(256) void mo_unpack_kernel(const uint32_t* __restri
 __global__ __launch_bounds__(256) void mo_popcount_kernel(const uint32_t* __restrict__ a, int64_t words, uint32_t* __restrict__ counter) {
     uint32_t c = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) c += (uint32_t)__popc(a[i]);
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+    c = wave_sum_u32(c);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(counter, c);
 }
 
@@ -138,89 +139,14 @@ __global__ __launch_bounds__(256) void mo_ball_kernel(const uint32_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ 6-connected components
-__device__ __forceinline__ uint32_t cc6_find(uint32_t* lab, uint32_t x) {
-    uint32_t p = lab[x];
-    while (p != x) {
-        const uint32_t g = lab[p];
-        if (g != p) lab[x] = g;      // path halving: only non-root entries are written, roots change by atomicMin alone
-        x = p;
-        p = g;
-    }
-    return x;
-}
-__device__ __forceinline__ void cc6_unite(uint32_t* lab, uint32_t a, uint32_t b) {
-    while (true) {
-        a = cc6_find(lab, a);
-        b = cc6_find(lab, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }      // hang the larger root under the smaller one
-        const uint32_t old = atomicMin(&lab[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// one wave per row: every foreground voxel starts as a child of the first voxel of its x-run; sizes are cleared on the way
-__global__ __launch_bounds__(256) void cc6_init_kernel(const uint8_t* __restrict__ m, uint32_t* __restrict__ lab, uint32_t* __restrict__ sizes,
-                                                       uint32_t* __restrict__ ov, int W, int64_t rows) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;                                   // wave-uniform
-    const int64_t base = row * W;
-    uint32_t carry = MO_NONE;
-    for (int x0 = 0; x0 < W; x0 += 64) {
-        const int x = x0 + lane;
-        const bool fg = x < W && m[base + x] != 0;
-        const unsigned long long mask = __ballot(fg);
-        uint32_t start = MO_NONE;
-        if (fg) {
-            const unsigned long long below_bg = ~mask & ((1ull << lane) - 1ull);
-            if (below_bg == 0ull) start = carry != MO_NONE ? carry : (uint32_t)(base + x0);
-            else start = (uint32_t)(base + x0 + (64 - __clzll(below_bg)));
-            lab[base + x] = start;
-        } else if (x < W) lab[base + x] = MO_NONE;
-        if (x < W) { sizes[base + x] = 0u; if (ov) ov[base + x] = 0u; }
-        carry = __shfl(start, 63, 64);
-    }
-}
-
 __global__ __launch_bounds__(256) void cc6_merge_kernel(const uint8_t* __restrict__ m, uint32_t* __restrict__ lab, int Z, int H, int W) {
     const int64_t n = (int64_t)Z * H * W;
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
         if (m[v] == 0) continue;
         const int64_t row = v / W;
         const int y = (int)(row % H), z = (int)(row / H);
-        if (y > 0 && m[v - W] != 0) cc6_unite(lab, (uint32_t)v, (uint32_t)(v - W));
-        if (z > 0 && m[v - (int64_t)H * W] != 0) cc6_unite(lab, (uint32_t)v, (uint32_t)(v - (int64_t)H * W));
-    }
-}
-
-__global__ __launch_bounds__(256) void cc6_flatten_kernel(uint32_t* __restrict__ lab, int64_t n) {
-    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
-        uint32_t p = lab[v];
-        if (p == MO_NONE) continue;
-        while (true) { const uint32_t g = lab[p]; if (g == p) break; p = g; }
-        lab[v] = p;
-    }
-}
-
-// consecutive foreground voxels of a row share their root: one atomic per x-run and 64-voxel chunk
-__global__ __launch_bounds__(256) void cc6_count_kernel(const uint32_t* __restrict__ lab, uint32_t* __restrict__ sizes, int W, int64_t rows) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int64_t base = row * W;
-    for (int x0 = 0; x0 < W; x0 += 64) {
-        const int x = x0 + lane;
-        const uint32_t r = x < W ? lab[base + x] : MO_NONE;
-        const bool fg = r != MO_NONE;
-        const unsigned long long mask = __ballot(fg);
-        const bool head = fg && (lane == 0 || !((mask >> (lane - 1)) & 1ull));
-        if (head) {
-            const unsigned long long above_bg = ~mask & ~((2ull << lane) - 1ull);
-            const int end = above_bg ? __ffsll((long long)above_bg) - 1 : 64;
-            atomicAdd(&sizes[r], (uint32_t)(end - lane));
-        }
+        if (y > 0 && m[v - W] != 0) ccl_unite(lab, (uint32_t)v, (uint32_t)(v - W));
+        if (z > 0 && m[v - (int64_t)H * W] != 0) ccl_unite(lab, (uint32_t)v, (uint32_t)(v - (int64_t)H * W));
     }
 }
 
@@ -231,7 +157,7 @@ __global__ __launch_bounds__(256) void cc6_overlap_kernel(const uint32_t* __rest
     const int64_t n = (int64_t)Z * H * W;
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
         const uint32_t r = lab[v];
-        if (r == MO_NONE || org[v] == 0) continue;
+        if (r == CCL_NONE || org[v] == 0) continue;
         const int x = (int)(v % W);
         const int64_t row = v / W;
         const int y = (int)(row % H), z = (int)(row / H);
@@ -253,14 +179,15 @@ __global__ __launch_bounds__(256) void cc6_filter_kernel(const uint8_t* m, const
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
         const uint32_t r = lab[v];
         uint8_t o = 0;
-        if (r != MO_NONE) {
+        if (r != CCL_NONE) {
             const uint32_t sz = sizes[r];
             const bool keep = sz >= min_size && (!ov || (uint64_t)ov[r] * 10u > (uint64_t)sz);     // overlap / size > 0.1
             if (keep) { o = m[v]; ++kv; if (r == (uint32_t)v) ++kc; }
         }
         out[v] = o;
     }
-    for (int o = 32; o > 0; o >>= 1) { kv += (uint32_t)__shfl_xor((int)kv, o, 64); kc += (uint32_t)__shfl_xor((int)kc, o, 64); }
+    kv = wave_sum_u32(kv);
+    kc = wave_sum_u32(kc);
     if ((threadIdx.x & 63) == 0) {
         if (kept_voxels && kv) atomicAdd(kept_voxels, kv);
         if (kept_comps && kc) atomicAdd(kept_comps, kc);
@@ -327,61 +254,6 @@ __global__ __launch_bounds__(256) void mo_bytes_op_kernel(const uint8_t* a, cons
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void mo_max_kernel(const T* __restrict__ lab, const uint8_t* __restrict__ zflag, int64_t plane, int64_t n,
-                                                     uint32_t* __restrict__ out) {
-    uint32_t m = 0;
-    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256)
-        if (zflag[v / plane]) m = max(m, (uint32_t)lab[v]);
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-
-// stats[v] = {count, zmin, ymin, xmin, zmax, ymax, xmax, -} over the planes whose z flag is set; one wave per 512-voxel piece of a
-// row, 8 voxels per lane, lanes that flush the same label combine first (the pattern of sm_stats_kernel, smooth3d.hip)
-template <typename T>
-__global__ __launch_bounds__(256) void mo_stats_kernel(const T* __restrict__ lab, const uint8_t* __restrict__ zflag, int W, int64_t rows, int H,
-                                                       uint32_t* __restrict__ stats) {
-    const int chunks = (W + 511) / 512;
-    const int64_t piece = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (piece >= rows * chunks) return;
-    const int64_t row = piece / chunks;
-    const uint32_t z = (uint32_t)(row / H), y = (uint32_t)(row % H);
-    if (!zflag[z]) return;                                      // wave-uniform
-    const int lane = threadIdx.x & 63;
-    const int xb = (int)(piece % chunks) * 512 + lane * 8;
-    const T* p = lab + row * W;
-    uint32_t cur = 0, cnt = 0, xlo = 0, xhi = 0;
-    for (int i = 0; i <= 8; ++i) {
-        const int x = xb + i;
-        const uint32_t v = (i < 8 && x < W) ? (uint32_t)p[x] : 0u;
-        const bool flush = (v != cur);
-        uint32_t pend = (flush && cur) ? cur : 0u;
-        while (true) {
-            const uint64_t any = __ballot(pend != 0);
-            if (!any) break;
-            const int leader = __ffsll((long long)any) - 1;
-            const uint32_t lv = (uint32_t)__shfl((int)pend, leader, 64);
-            const bool mine = (pend == lv);
-            uint32_t c = mine ? cnt : 0u, lo = mine ? xlo : 0xffffffffu, hi = mine ? xhi : 0u;
-            for (int o = 32; o > 0; o >>= 1) {
-                c += (uint32_t)__shfl_xor((int)c, o, 64);
-                lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
-                hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
-            }
-            if (lane == leader) {
-                uint32_t* s = stats + (size_t)lv * 8;
-                atomicAdd(s + 0, c);
-                atomicMin(s + 1, z); atomicMin(s + 2, y); atomicMin(s + 3, lo);
-                atomicMax(s + 4, z); atomicMax(s + 5, y); atomicMax(s + 6, hi);
-            }
-            if (mine) pend = 0;
-        }
-        if (flush) { cur = v; cnt = 0; xlo = (uint32_t)x; }
-        if (v) { ++cnt; xhi = (uint32_t)x; }
-    }
-}
-
 // a finished pair into the two label maps (refine_membranes.py:433-442 + convert_to_3d_labels :549-573): launches follow each other in
 // ascending label order on one stream, so a later organelle overwrites an earlier one exactly as a later plane of the 4-D stack does.
 // Nothing is written when the organelle was dropped (*kept == 0: no membrane left after cleaning).
@@ -438,8 +310,6 @@ MoState* mo_state(saber_engine* e) {
     return (MoState*)e->refine_state;
 }
 
-inline unsigned mo_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
-
 // the (dz,dy) offsets of the ball in descending half-length of their x-run
 hipError_t mo_ball_table(MoState* S, int r, hipStream_t s, const int** out) {
     if (!S->tab_dev[r]) {
@@ -493,12 +363,12 @@ struct CcWs { uint32_t *lab = nullptr, *sizes = nullptr, *ov = nullptr; unsigned
 hipError_t cc6_run(const CcWs& w, const uint8_t* m, int Z, int H, int W, int mode, uint32_t min_size, const uint8_t* org, uint8_t* out,
                    uint32_t* kept_voxels, uint32_t* comps, hipStream_t s) {
     const int64_t n = (int64_t)Z * H * W, rows = (int64_t)Z * H;
-    const unsigned row_blocks = (unsigned)((rows + 3) / 4), vox_blocks = mo_blocks(n);
+    const unsigned vox_blocks = eng_blocks(n);
     uint32_t* ov = (mode == 0 && org) ? w.ov : nullptr;
-    hipLaunchKernelGGL(cc6_init_kernel, dim3(row_blocks), dim3(256), 0, s, m, w.lab, w.sizes, ov, W, rows);
+    ccl_init(m, w.lab, w.sizes, ov, W, rows, s);
     hipLaunchKernelGGL(cc6_merge_kernel, dim3(vox_blocks), dim3(256), 0, s, m, w.lab, Z, H, W);
-    hipLaunchKernelGGL(cc6_flatten_kernel, dim3(vox_blocks), dim3(256), 0, s, w.lab, n);
-    hipLaunchKernelGGL(cc6_count_kernel, dim3(row_blocks), dim3(256), 0, s, (const uint32_t*)w.lab, w.sizes, W, rows);
+    ccl_flatten(w.lab, n, vox_blocks, s);
+    ccl_count(w.lab, w.sizes, W, rows, s);
     if (mode == 0) {
         if (ov) hipLaunchKernelGGL(cc6_overlap_kernel, dim3(vox_blocks), dim3(256), 0, s, (const uint32_t*)w.lab, org, ov, Z, H, W);
         hipLaunchKernelGGL(cc6_filter_kernel, dim3(vox_blocks), dim3(256), 0, s, m, (const uint32_t*)w.lab, (const uint32_t*)w.sizes, (const uint32_t*)ov,
@@ -524,7 +394,7 @@ inline void mo_pack_bytes(const uint8_t* src, int dz, int dy, int dx, uint32_t* 
 inline void mo_unpack(const uint32_t* a, const uint32_t* b, const uint32_t* alt, const uint32_t* counter, int dz, int dy, int dx, uint8_t* out,
                       hipStream_t s) {
     const int64_t rows = (int64_t)dz * dy;
-    hipLaunchKernelGGL(mo_unpack_kernel, dim3(mo_blocks(rows * dx)), dim3(256), 0, s, a, b, alt, counter, rows, dx, (dx + 31) / 32, out);
+    hipLaunchKernelGGL(mo_unpack_kernel, dim3(eng_blocks(rows * dx)), dim3(256), 0, s, a, b, alt, counter, rows, dx, (dx + 31) / 32, out);
 }
 }  // namespace
 
@@ -536,12 +406,6 @@ void refine_release(saber_engine* e) {
     delete S;
     e->refine_state = nullptr;
 }
-
-#define MO_HIP(e, call)                                                                                                  \
-    do {                                                                                                                 \
-        hipError_t _st = (call);                                                                                         \
-        if (_st != hipSuccess) { cleanup(); return eng_fail((e), SABER_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); } \
-    } while (0)
 
 extern "C" int saber_morph_ball_3d(saber_engine* e, const uint8_t* mask_dev, int Z, int H, int W, int radius, int op, uint8_t* out_dev,
                                    void* stream) {
@@ -556,15 +420,15 @@ extern "C" int saber_morph_ball_3d(saber_engine* e, const uint8_t* mask_dev, int
     ENG_DEVICE(e);
     MoState* S = mo_state(e);
     const size_t words = (size_t)Z * H * ((W + 31) / 32);
-    MO_HIP(e, mo_ball_attrs());
-    MO_HIP(e, hipMalloc(&pa, words * 4));
-    MO_HIP(e, hipMalloc(&pb, words * 4));
+    ENG_HIP_CLEANUP(e, mo_ball_attrs());
+    ENG_HIP_CLEANUP(e, hipMalloc(&pa, words * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&pb, words * 4));
     mo_pack_bytes(mask_dev, Z, H, W, pa, s);
-    MO_HIP(e, mo_ball(S, pa, pb, Z, H, W, radius, op != 0, s));
-    if (op == 2) MO_HIP(e, mo_ball(S, pb, pa, Z, H, W, radius, false, s));
+    ENG_HIP_CLEANUP(e, mo_ball(S, pa, pb, Z, H, W, radius, op != 0, s));
+    if (op == 2) ENG_HIP_CLEANUP(e, mo_ball(S, pb, pa, Z, H, W, radius, false, s));
     mo_unpack(op == 2 ? pa : pb, nullptr, nullptr, nullptr, Z, H, W, out_dev, s);
-    MO_HIP(e, hipGetLastError());
-    MO_HIP(e, hipStreamSynchronize(s));
+    ENG_HIP_CLEANUP(e, hipGetLastError());
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
     cleanup();
     return SABER_OK;
 }
@@ -582,15 +446,15 @@ extern "C" int saber_components6_3d(saber_engine* e, const uint8_t* mask_dev, in
     auto cleanup = [&]() { (void)hipFree(w.lab); (void)hipFree(w.sizes); (void)hipFree(w.best); (void)hipFree(counter); };
     ENG_DEVICE(e);
     if (out_n_components) *out_n_components = 0;
-    MO_HIP(e, hipMalloc(&w.lab, (size_t)n * 4));
-    MO_HIP(e, hipMalloc(&w.sizes, (size_t)n * 4));
-    MO_HIP(e, hipMalloc(&w.best, 8));
-    MO_HIP(e, hipMalloc(&counter, 4));
-    MO_HIP(e, hipMemsetAsync(counter, 0, 4, s));
-    MO_HIP(e, cc6_run(w, mask_dev, Z, H, W, mode, (uint32_t)std::max(min_size, 0), nullptr, out_dev, nullptr, counter, s));
+    ENG_HIP_CLEANUP(e, hipMalloc(&w.lab, (size_t)n * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&w.sizes, (size_t)n * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&w.best, 8));
+    ENG_HIP_CLEANUP(e, hipMalloc(&counter, 4));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(counter, 0, 4, s));
+    ENG_HIP_CLEANUP(e, cc6_run(w, mask_dev, Z, H, W, mode, (uint32_t)std::max(min_size, 0), nullptr, out_dev, nullptr, counter, s));
     uint32_t k = 0;
-    MO_HIP(e, hipMemcpyAsync(&k, counter, 4, hipMemcpyDeviceToHost, s));
-    MO_HIP(e, hipStreamSynchronize(s));
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&k, counter, 4, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
     cleanup();
     if (out_n_components) *out_n_components = (int)k;        // mode 0: components kept; mode 1: components found
     return SABER_OK;
@@ -620,37 +484,37 @@ int refine_run(saber_engine* e, const T* org, const uint8_t* mem, int Z, int H, 
     MoState* S = mo_state(e);
     // the pairs of the previous call go now
     S->pairs.clear();
-    MO_HIP(e, hipStreamSynchronize(s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
     (void)hipFree(S->bits);
     S->bits = nullptr;
     S->Z = Z; S->H = H; S->W = W;
-    MO_HIP(e, mo_ball_attrs());
-    MO_HIP(e, hipMemsetAsync(org_out, 0, (size_t)n * sizeof(T), s));
-    MO_HIP(e, hipMemsetAsync(mem_out, 0, (size_t)n * sizeof(T), s));
+    ENG_HIP_CLEANUP(e, mo_ball_attrs());
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(org_out, 0, (size_t)n * sizeof(T), s));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(mem_out, 0, (size_t)n * sizeof(T), s));
     // ---- step 1 (run, :466-471): trim the membrane, drop its 6-connected components below min_membrane_area
-    MO_HIP(e, hipMalloc(&R.trim, (size_t)n));
-    MO_HIP(e, hipMalloc(&R.clean, (size_t)n));
-    MO_HIP(e, hipMalloc(&R.zflag, (size_t)Z));
-    MO_HIP(e, hipMalloc(&R.cc.lab, (size_t)n * 4));
-    MO_HIP(e, hipMalloc(&R.cc.sizes, (size_t)n * 4));
-    MO_HIP(e, hipMalloc(&R.cc.best, 8));
-    MO_HIP(e, hipMalloc(&R.maxv, 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.trim, (size_t)n));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.clean, (size_t)n));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.zflag, (size_t)Z));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.cc.lab, (size_t)n * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.cc.sizes, (size_t)n * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.cc.best, 8));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.maxv, 4));
     const int tz = P->edge_trim_z, txy = P->edge_trim_xy;
     int z0 = 0, z1 = 0, y0 = 0, y1 = 0, x0 = 0, x1 = 0;        // empty boxes unless the trims are usable
     if (tz > 0 && tz < Z / 2) { z0 = tz; z1 = Z - tz; }
     if (txy > 0 && txy < H / 2 && txy < W / 2) { y0 = txy; y1 = H - txy; x0 = txy; x1 = W - txy; }
-    hipLaunchKernelGGL(mo_trim_kernel, dim3(mo_blocks(n)), dim3(256), 0, s, mem, R.trim, Z, H, W, z0, z1, y0, y1, x0, x1);
-    MO_HIP(e, cc6_run(R.cc, R.trim, Z, H, W, 0, (uint32_t)std::max(P->min_membrane_area, 0), nullptr, R.clean, nullptr, nullptr, s));
+    hipLaunchKernelGGL(mo_trim_kernel, dim3(eng_blocks(n)), dim3(256), 0, s, mem, R.trim, Z, H, W, z0, z1, y0, y1, x0, x1);
+    ENG_HIP_CLEANUP(e, cc6_run(R.cc, R.trim, Z, H, W, 0, (uint32_t)std::max(P->min_membrane_area, 0), nullptr, R.clean, nullptr, nullptr, s));
     // ---- step 2 (:473-476): organelles only count on planes that hold membrane
-    MO_HIP(e, hipMemsetAsync(R.zflag, 0, (size_t)Z, s));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(R.zflag, 0, (size_t)Z, s));
     hipLaunchKernelGGL(mo_zpresence_kernel, dim3((unsigned)std::min<int64_t>((plane + 255) / 256, 64), Z), dim3(256), 0, s, (const uint8_t*)R.clean, plane,
                        R.zflag);
     // ---- step 3 (:478-480): the labels present, with voxel count and bounding box
-    MO_HIP(e, hipMemsetAsync(R.maxv, 0, 4, s));
-    hipLaunchKernelGGL(mo_max_kernel<T>, dim3(mo_blocks(n)), dim3(256), 0, s, org, (const uint8_t*)R.zflag, plane, n, R.maxv);
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(R.maxv, 0, 4, s));
+    label_max(org, sizeof(T), R.zflag, plane, n, R.maxv, s);
     uint32_t maxv = 0;
-    MO_HIP(e, hipMemcpyAsync(&maxv, R.maxv, 4, hipMemcpyDeviceToHost, s));
-    MO_HIP(e, hipStreamSynchronize(s));                        // synchronisation 1
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, R.maxv, 4, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                        // synchronisation 1
     if (maxv == 0) { cleanup(); return SABER_OK; }
     if (maxv > MO_MAX_LABEL) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "refine_membranes: label values above 2^22 are not supported"); }
     const uint64_t type_max = sizeof(T) == 1 ? 0xffull : (sizeof(T) == 2 ? 0xffffull : 0xffffffffull);
@@ -662,15 +526,12 @@ int refine_run(saber_engine* e, const T* org, const uint8_t* mem, int Z, int H, 
     const size_t n_stats = (size_t)maxv + 1;
     std::vector<uint32_t> st(n_stats * 8);
     for (size_t v = 0; v < n_stats; ++v) { uint32_t* p = &st[v * 8]; p[0] = 0; p[1] = p[2] = p[3] = 0xffffffffu; p[4] = p[5] = p[6] = p[7] = 0; }
-    MO_HIP(e, hipMalloc(&R.stats, n_stats * 32));
-    MO_HIP(e, hipMemcpyAsync(R.stats, st.data(), n_stats * 32, hipMemcpyHostToDevice, s));
-    {
-        const int64_t rows = (int64_t)Z * H, pieces = rows * ((W + 511) / 512);
-        hipLaunchKernelGGL(mo_stats_kernel<T>, dim3((unsigned)((pieces + 3) / 4)), dim3(256), 0, s, org, (const uint8_t*)R.zflag, W, rows, H, R.stats);
-    }
-    MO_HIP(e, hipGetLastError());
-    MO_HIP(e, hipMemcpyAsync(st.data(), R.stats, n_stats * 32, hipMemcpyDeviceToHost, s));
-    MO_HIP(e, hipStreamSynchronize(s));                        // synchronisation 2
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.stats, n_stats * 32));
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(R.stats, st.data(), n_stats * 32, hipMemcpyHostToDevice, s));
+    label_stats(org, sizeof(T), R.zflag, Z, H, W, R.stats, s);
+    ENG_HIP_CLEANUP(e, hipGetLastError());
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(st.data(), R.stats, n_stats * 32, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                        // synchronisation 2
     // ---- host: ROI per label (_get_organelle_roi, :251-272) and the shape-dependent radii (:364-374)
     std::vector<RfCand> cands;
     const int pad = P->ball_size / 2;
@@ -706,20 +567,20 @@ int refine_run(saber_engine* e, const T* org, const uint8_t* mem, int Z, int H, 
         cands.push_back(c);
     }
     if (out_n_labels_in) *out_n_labels_in = n_in;
-    if (cands.empty()) { MO_HIP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
-    MO_HIP(e, hipMalloc(&S->bits, bit_words * 4));
-    MO_HIP(e, hipMalloc(&R.flags, cands.size() * 8));
-    MO_HIP(e, hipMemsetAsync(R.flags, 0, cands.size() * 8, s));
-    MO_HIP(e, hipMalloc(&R.b_org, (size_t)roi_max));
-    MO_HIP(e, hipMalloc(&R.b_cl, (size_t)roi_max));
-    MO_HIP(e, hipMalloc(&R.b_comb, (size_t)roi_max));
-    MO_HIP(e, hipMalloc(&R.b_t, (size_t)roi_max));
-    if (P->keep_surface_membranes) MO_HIP(e, hipMalloc(&R.cc.ov, (size_t)roi_max * 4));
-    MO_HIP(e, hipMalloc(&R.p_org, roi_words_max * 4));
-    MO_HIP(e, hipMalloc(&R.p_mem, roi_words_max * 4));
-    MO_HIP(e, hipMalloc(&R.p_a, roi_words_max * 4));
-    MO_HIP(e, hipMalloc(&R.p_b, roi_words_max * 4));
-    MO_HIP(e, hipMalloc(&R.p_c, roi_words_max * 4));
+    if (cands.empty()) { ENG_HIP_CLEANUP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
+    ENG_HIP_CLEANUP(e, hipMalloc(&S->bits, bit_words * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.flags, cands.size() * 8));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(R.flags, 0, cands.size() * 8, s));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.b_org, (size_t)roi_max));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.b_cl, (size_t)roi_max));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.b_comb, (size_t)roi_max));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.b_t, (size_t)roi_max));
+    if (P->keep_surface_membranes) ENG_HIP_CLEANUP(e, hipMalloc(&R.cc.ov, (size_t)roi_max * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.p_org, roi_words_max * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.p_mem, roi_words_max * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.p_a, roi_words_max * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.p_b, roi_words_max * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&R.p_c, roi_words_max * 4));
     // ---- per organelle, ascending label (_process_organelle_batch, :335-443); nothing below waits for the device
     for (size_t i = 0; i < cands.size(); ++i) {
         const RfCand& c = cands[i];
@@ -728,40 +589,40 @@ int refine_run(saber_engine* e, const T* org, const uint8_t* mem, int Z, int H, 
         const int64_t origin = ((int64_t)c.p.z0 * H + c.p.y0) * W + c.p.x0;
         uint32_t* kept = R.flags + 2 * i;                       // voxels of the cleaned membrane: 0 = the organelle is dropped (:384, :399)
         uint32_t* opened = R.flags + 2 * i + 1;                 // voxels the opening left: 0 = fall back to the unopened mask (:414-416)
-        const unsigned vb = mo_blocks(rn);
+        const unsigned vb = eng_blocks(rn);
         mo_pack<T, true>(org + origin, plane, W, c.p.label, R.zflag + c.p.z0, dz, dy, dx, R.p_org, s);
         mo_pack<uint8_t, false>(R.clean + origin, plane, W, 0u, nullptr, dz, dy, dx, R.p_mem, s);
         // enhanced membrane = dilate(membrane) AND dilate(organelle)   (:376-382)
-        MO_HIP(e, mo_ball(S, R.p_mem, R.p_a, dz, dy, dx, c.dilate_r, false, s));
-        MO_HIP(e, mo_ball(S, R.p_org, R.p_b, dz, dy, dx, c.dilate_r, false, s));
+        ENG_HIP_CLEANUP(e, mo_ball(S, R.p_mem, R.p_a, dz, dy, dx, c.dilate_r, false, s));
+        ENG_HIP_CLEANUP(e, mo_ball(S, R.p_org, R.p_b, dz, dy, dx, c.dilate_r, false, s));
         mo_unpack(R.p_a, R.p_b, nullptr, nullptr, dz, dy, dx, R.b_t, s);
         mo_unpack(R.p_org, nullptr, nullptr, nullptr, dz, dy, dx, R.b_org, s);
         // components >= 100 voxels (:393), on the organelle's surface when asked (:396-397)
-        MO_HIP(e, cc6_run(R.cc, R.b_t, dz, dy, dx, 0, 100u, P->keep_surface_membranes ? R.b_org : nullptr, R.b_cl, kept, nullptr, s));
+        ENG_HIP_CLEANUP(e, cc6_run(R.cc, R.b_t, dz, dy, dx, 0, 100u, P->keep_surface_membranes ? R.b_org : nullptr, R.b_cl, kept, nullptr, s));
         // combined = (organelle - membrane) != 0: the organelle's value is >= 4, so this is organelle OR membrane (:403-408)
         hipLaunchKernelGGL(mo_bytes_op_kernel, dim3(vb), dim3(256), 0, s, (const uint8_t*)R.b_org, (const uint8_t*)R.b_cl, 0, R.b_comb, rn);
         mo_pack_bytes(R.b_comb, dz, dy, dx, R.p_a, s);
         // opening (:410-420), then its largest component (:423)
-        MO_HIP(e, mo_ball(S, R.p_a, R.p_b, dz, dy, dx, c.open_r, true, s));
-        MO_HIP(e, mo_ball(S, R.p_b, R.p_c, dz, dy, dx, c.open_r, false, s));
-        hipLaunchKernelGGL(mo_popcount_kernel, dim3(mo_blocks(words)), dim3(256), 0, s, (const uint32_t*)R.p_c, words, opened);
+        ENG_HIP_CLEANUP(e, mo_ball(S, R.p_a, R.p_b, dz, dy, dx, c.open_r, true, s));
+        ENG_HIP_CLEANUP(e, mo_ball(S, R.p_b, R.p_c, dz, dy, dx, c.open_r, false, s));
+        hipLaunchKernelGGL(mo_popcount_kernel, dim3(eng_blocks(words)), dim3(256), 0, s, (const uint32_t*)R.p_c, words, opened);
         mo_unpack(R.p_c, nullptr, R.p_a, opened, dz, dy, dx, R.b_comb, s);
-        MO_HIP(e, cc6_run(R.cc, R.b_comb, dz, dy, dx, 1, 0u, nullptr, R.b_comb, nullptr, nullptr, s));
+        ENG_HIP_CLEANUP(e, cc6_run(R.cc, R.b_comb, dz, dy, dx, 1, 0u, nullptr, R.b_comb, nullptr, nullptr, s));
         // organelle AND combined -> largest component (:426-427); membrane AND combined -> components >= 50 voxels (:430-431)
         hipLaunchKernelGGL(mo_bytes_op_kernel, dim3(vb), dim3(256), 0, s, (const uint8_t*)R.b_org, (const uint8_t*)R.b_comb, 1, R.b_t, rn);
-        MO_HIP(e, cc6_run(R.cc, R.b_t, dz, dy, dx, 1, 0u, nullptr, R.b_t, nullptr, nullptr, s));
+        ENG_HIP_CLEANUP(e, cc6_run(R.cc, R.b_t, dz, dy, dx, 1, 0u, nullptr, R.b_t, nullptr, nullptr, s));
         hipLaunchKernelGGL(mo_bytes_op_kernel, dim3(vb), dim3(256), 0, s, (const uint8_t*)R.b_cl, (const uint8_t*)R.b_comb, 1, R.b_cl, rn);
-        MO_HIP(e, cc6_run(R.cc, R.b_cl, dz, dy, dx, 0, 50u, nullptr, R.b_cl, nullptr, nullptr, s));
+        ENG_HIP_CLEANUP(e, cc6_run(R.cc, R.b_cl, dz, dy, dx, 0, 50u, nullptr, R.b_cl, nullptr, nullptr, s));
         // keep the pair compactly, write it into the label maps: organelle v comes out as v + 1 (:494-495, :437, :539-540)
         mo_pack_bytes(R.b_t, dz, dy, dx, S->bits + c.p.off_org, s);
         mo_pack_bytes(R.b_cl, dz, dy, dx, S->bits + c.p.off_mem, s);
         hipLaunchKernelGGL(mo_scatter_kernel<T>, dim3(vb), dim3(256), 0, s, (const uint8_t*)R.b_t, (const uint8_t*)R.b_cl, (const uint32_t*)kept,
                            (T)(c.p.label + 1), dz, dy, dx, H, W, c.p.z0, c.p.y0, c.p.x0, org_out, mem_out);
-        MO_HIP(e, hipGetLastError());
+        ENG_HIP_CLEANUP(e, hipGetLastError());
     }
     std::vector<uint32_t> flags(cands.size() * 2);
-    MO_HIP(e, hipMemcpyAsync(flags.data(), R.flags, flags.size() * 4, hipMemcpyDeviceToHost, s));
-    MO_HIP(e, hipStreamSynchronize(s));                        // synchronisation 3
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(flags.data(), R.flags, flags.size() * 4, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                        // synchronisation 3
     for (size_t i = 0; i < cands.size(); ++i)
         if (flags[2 * i]) S->pairs.push_back(cands[i].p);
     if (out_n_pairs) *out_n_pairs = (int)S->pairs.size();
@@ -796,7 +657,7 @@ static void mo_expand_pairs(const MoState* S, int first, int count, T* org_stack
     for (int k = 0; k < count; ++k) {
         const MoPair& p = S->pairs[first + k];
         const int WW = (p.dx + 31) / 32;
-        const unsigned vb = mo_blocks((int64_t)p.dz * p.dy * p.dx);
+        const unsigned vb = eng_blocks((int64_t)p.dz * p.dy * p.dx);
         hipLaunchKernelGGL(mo_expand_kernel<T>, dim3(vb), dim3(256), 0, s, (const uint32_t*)(S->bits + p.off_org), (T)(p.label + 1), p.dz, p.dy, p.dx, WW,
                            S->H, S->W, p.z0, p.y0, p.x0, org_stack + (int64_t)k * n);
         hipLaunchKernelGGL(mo_expand_kernel<T>, dim3(vb), dim3(256), 0, s, (const uint32_t*)(S->bits + p.off_mem), (T)(p.label + 1), p.dz, p.dy, p.dx, WW,

@@ -20,6 +20,7 @@
 #include <cmath>
 #include <vector>
 
+#include "common.h"
 #include "engine.h"
 
 struct SmLabel {
@@ -34,25 +35,30 @@ struct SmLabel {
 #define SM_TL 32        // outputs per block along the convolved axis
 #define SM_TX 64        // x columns per block
 
-template <typename T>
-__global__ __launch_bounds__(256) void sm_max_kernel(const T* __restrict__ lab, int64_t n, uint32_t* __restrict__ out) {
+// ZFLAG (both kernels): only the planes whose z flag is set count (morph3d.hip: organelles count where there is membrane)
+template <typename T, bool ZFLAG>
+__global__ __launch_bounds__(256) void sm_max_kernel(const T* __restrict__ lab, const uint8_t* __restrict__ zflag, int64_t plane, int64_t n,
+                                                     uint32_t* __restrict__ out) {
     uint32_t m = 0;
-    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) m = max(m, (uint32_t)lab[v]);
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256)
+        if (!ZFLAG || zflag[v / plane]) m = max(m, (uint32_t)lab[v]);
+    m = wave_max_u32(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
 // stats[v] = {count, zmin, ymin, xmin, zmax, ymax, xmax, -}; one wave per 512-voxel piece of a row, 8 voxels per lane.
-template <typename T>
-__global__ __launch_bounds__(256) void sm_stats_kernel(const T* __restrict__ lab, int W, int64_t rows, int H, uint32_t* __restrict__ stats) {
+template <typename T, bool ZFLAG>
+__global__ __launch_bounds__(256) void sm_stats_kernel(const T* __restrict__ lab, const uint8_t* __restrict__ zflag, int W, int64_t rows, int H,
+                                                       uint32_t* __restrict__ stats) {
     const int chunks = (W + 511) / 512;
     const int64_t piece = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (piece >= rows * chunks) return;
     const int64_t row = piece / chunks;
+    const uint32_t z = (uint32_t)(row / H), y = (uint32_t)(row % H);
+    if (ZFLAG && !zflag[z]) return;                             // wave-uniform
     const int lane = threadIdx.x & 63;
     const int xb = (int)(piece % chunks) * 512 + lane * 8;
     const T* p = lab + row * W;
-    const uint32_t z = (uint32_t)(row / H), y = (uint32_t)(row % H);
     // runs inside this lane's 8 voxels; a run is flushed through the wave: lanes holding the same label combine first
     uint32_t cur = 0, cnt = 0, xlo = 0, xhi = 0;
     for (int i = 0; i <= 8; ++i) {
@@ -67,7 +73,7 @@ __global__ __launch_bounds__(256) void sm_stats_kernel(const T* __restrict__ lab
             const uint32_t lv = (uint32_t)__shfl((int)pend, leader, 64);
             const bool mine = (pend == lv);
             uint32_t c = mine ? cnt : 0u, lo = mine ? xlo : 0xffffffffu, hi = mine ? xhi : 0u;
-            for (int o = 32; o > 0; o >>= 1) {
+            for (int o = 32; o > 0; o >>= 1) {                  // one ladder for the three: their shuffles of a step are in flight together
                 c += (uint32_t)__shfl_xor((int)c, o, 64);
                 lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
                 hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
@@ -205,12 +211,6 @@ static int sm_make_taps(double sigma, std::vector<float>& out) {
     return r;
 }
 
-#define SM_HIP(e, call)                                                                                                  \
-    do {                                                                                                                 \
-        hipError_t _st = (call);                                                                                         \
-        if (_st != hipSuccess) { cleanup(); return eng_fail((e), SABER_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); } \
-    } while (0)
-
 #define SM_MAX_LABEL (1u << 22)
 #define SM_LDS_LIMIT (150 * 1024)
 
@@ -226,22 +226,37 @@ struct SmScratch {
 };
 
 template <typename T>
-void sm_launch_stats(const T* lab, int Z, int H, int W, uint32_t* stats, hipStream_t s) {
-    const int64_t rows = (int64_t)Z * H;
-    const int64_t pieces = rows * ((W + 511) / 512);
-    hipLaunchKernelGGL(sm_stats_kernel<T>, dim3((unsigned)((pieces + 3) / 4)), dim3(256), 0, s, lab, W, rows, H, stats);
-}
-template <typename T>
-void sm_launch_max(const T* lab, int64_t n, uint32_t* out, hipStream_t s) {
-    hipLaunchKernelGGL(sm_max_kernel<T>, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1 << 16)), dim3(256), 0, s, lab, n, out);
-}
-template <typename T>
 void sm_launch_conv_x(const T* vol, int H, int W, const SmLabel* labels, const int* prefix, int n, int tiles, int rmax, const float* taps,
                       float* ws, hipStream_t s) {
     hipLaunchKernelGGL(sm_conv_x_kernel<T>, dim3(tiles), dim3(256), (size_t)4 * (64 + 2 * rmax) * sizeof(float), s, vol, H, W, labels, prefix,
                        n, taps, ws);
 }
+
+template <typename T>
+void sm_launch_max(const T* lab, const uint8_t* zflag, int64_t plane, int64_t n, uint32_t* out, hipStream_t s) {
+    if (zflag) hipLaunchKernelGGL((sm_max_kernel<T, true>), dim3(eng_blocks(n)), dim3(256), 0, s, lab, zflag, plane, n, out);
+    else hipLaunchKernelGGL((sm_max_kernel<T, false>), dim3(eng_blocks(n)), dim3(256), 0, s, lab, zflag, plane, n, out);
+}
+template <typename T>
+void sm_launch_stats(const T* lab, const uint8_t* zflag, int Z, int H, int W, uint32_t* stats, hipStream_t s) {
+    const int64_t rows = (int64_t)Z * H;
+    const unsigned grid = (unsigned)((rows * ((W + 511) / 512) + 3) / 4);
+    if (zflag) hipLaunchKernelGGL((sm_stats_kernel<T, true>), dim3(grid), dim3(256), 0, s, lab, zflag, W, rows, H, stats);
+    else hipLaunchKernelGGL((sm_stats_kernel<T, false>), dim3(grid), dim3(256), 0, s, lab, zflag, W, rows, H, stats);
+}
 }  // namespace
+
+void label_max(const void* lab, int elem_bytes, const uint8_t* zflag, int64_t plane, int64_t n, uint32_t* out, hipStream_t s) {
+    if (elem_bytes == 1) sm_launch_max((const uint8_t*)lab, zflag, plane, n, out, s);
+    else if (elem_bytes == 2) sm_launch_max((const uint16_t*)lab, zflag, plane, n, out, s);
+    else sm_launch_max((const uint32_t*)lab, zflag, plane, n, out, s);
+}
+
+void label_stats(const void* lab, int elem_bytes, const uint8_t* zflag, int Z, int H, int W, uint32_t* stats, hipStream_t s) {
+    if (elem_bytes == 1) sm_launch_stats((const uint8_t*)lab, zflag, Z, H, W, stats, s);
+    else if (elem_bytes == 2) sm_launch_stats((const uint16_t*)lab, zflag, Z, H, W, stats, s);
+    else sm_launch_stats((const uint32_t*)lab, zflag, Z, H, W, stats, s);
+}
 
 // mode 0: label volume -> uint8 (fast_3d_gaussian_smoothing);  mode 1: binary mask (any non-zero) + fixed sigma -> float field
 static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, int H, int W, double scale, double fixed_sigma, int mode,
@@ -251,30 +266,26 @@ static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, i
     auto cleanup = [&]() { S.release(); };
     ENG_DEVICE(e);
     if (out_n_labels) *out_n_labels = 0;
-    SM_HIP(e, hipMalloc(&S.maxv, 4));
-    SM_HIP(e, hipMemsetAsync(S.maxv, 0, 4, s));
-    if (elem_bytes == 1) sm_launch_max((const uint8_t*)vol_dev, n, S.maxv, s);
-    else if (elem_bytes == 2) sm_launch_max((const uint16_t*)vol_dev, n, S.maxv, s);
-    else sm_launch_max((const uint32_t*)vol_dev, n, S.maxv, s);
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
+    label_max(vol_dev, elem_bytes, nullptr, 0, n, S.maxv, s);
     uint32_t maxv = 0;
-    SM_HIP(e, hipMemcpyAsync(&maxv, S.maxv, 4, hipMemcpyDeviceToHost, s));
-    SM_HIP(e, hipStreamSynchronize(s));
-    if (mode == 0) SM_HIP(e, hipMemsetAsync(out_dev, 0, (size_t)n, s));
-    else SM_HIP(e, hipMemsetAsync(out_dev, 0, (size_t)n * 4, s));
-    if (maxv == 0) { SM_HIP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, S.maxv, 4, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    if (mode == 0) ENG_HIP_CLEANUP(e, hipMemsetAsync(out_dev, 0, (size_t)n, s));
+    else ENG_HIP_CLEANUP(e, hipMemsetAsync(out_dev, 0, (size_t)n * 4, s));
+    if (maxv == 0) { ENG_HIP_CLEANUP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
     if (maxv > SM_MAX_LABEL) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "smooth_labels: label values above 2^22 are not supported"); }
     // ---- per-label count + bounding box
     const size_t n_stats = (size_t)maxv + 1;
     std::vector<uint32_t> st(n_stats * 8);
     for (size_t v = 0; v < n_stats; ++v) { uint32_t* p = &st[v * 8]; p[0] = 0; p[1] = p[2] = p[3] = 0xffffffffu; p[4] = p[5] = p[6] = p[7] = 0; }
-    SM_HIP(e, hipMalloc(&S.stats, n_stats * 32));
-    SM_HIP(e, hipMemcpyAsync(S.stats, st.data(), n_stats * 32, hipMemcpyHostToDevice, s));
-    if (elem_bytes == 1) sm_launch_stats((const uint8_t*)vol_dev, Z, H, W, S.stats, s);
-    else if (elem_bytes == 2) sm_launch_stats((const uint16_t*)vol_dev, Z, H, W, S.stats, s);
-    else sm_launch_stats((const uint32_t*)vol_dev, Z, H, W, S.stats, s);
-    SM_HIP(e, hipGetLastError());
-    SM_HIP(e, hipMemcpyAsync(st.data(), S.stats, n_stats * 32, hipMemcpyDeviceToHost, s));
-    SM_HIP(e, hipStreamSynchronize(s));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.stats, n_stats * 32));
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.stats, st.data(), n_stats * 32, hipMemcpyHostToDevice, s));
+    label_stats(vol_dev, elem_bytes, nullptr, Z, H, W, S.stats, s);
+    ENG_HIP_CLEANUP(e, hipGetLastError());
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(st.data(), S.stats, n_stats * 32, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
     // ---- host: sigma, radius, taps per present label, ascending label value (np.unique order, masks.py:253-262)
     std::vector<SmLabel> labs;
     std::vector<float> taps(SM_OPT - 1, 0.0f);
@@ -311,18 +322,18 @@ static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, i
     int64_t total = 0;
     for (auto& L : labs) total += 2 * (int64_t)L.dz * L.dy * L.dx;
     const int64_t ws_floats = std::min(total, std::max<int64_t>(2 * biggest, (int64_t)1 << 28));
-    SM_HIP(e, hipMalloc(&S.ws, (size_t)ws_floats * 4));
-    SM_HIP(e, hipMalloc(&S.taps, taps.size() * 4));
-    SM_HIP(e, hipMemcpyAsync(S.taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
-    SM_HIP(e, hipMalloc(&S.labels, labs.size() * sizeof(SmLabel)));
-    SM_HIP(e, hipMalloc(&S.prefix, 3 * (labs.size() + 1) * sizeof(int)));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.ws, (size_t)ws_floats * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.taps, taps.size() * 4));
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.labels, labs.size() * sizeof(SmLabel)));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.prefix, 3 * (labs.size() + 1) * sizeof(int)));
     if (mode == 0) {
-        SM_HIP(e, hipMalloc(&S.winner, (size_t)n * 4));
-        SM_HIP(e, hipMemsetAsync(S.winner, 0, (size_t)n * 4, s));
+        ENG_HIP_CLEANUP(e, hipMalloc(&S.winner, (size_t)n * 4));
+        ENG_HIP_CLEANUP(e, hipMemsetAsync(S.winner, 0, (size_t)n * 4, s));
     }
-    SM_HIP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
-    SM_HIP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
-    SM_HIP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
     std::vector<int> prefix;
     size_t g0 = 0;
     while (g0 < labs.size()) {
@@ -351,8 +362,8 @@ static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, i
         }
         const int ng = (int)(g1 - g0);
         for (int a = 0; a < 3; ++a) prefix[a * stride + ng] = (int)tiles[a];
-        SM_HIP(e, hipMemcpyAsync(S.labels, labs.data() + g0, (size_t)ng * sizeof(SmLabel), hipMemcpyHostToDevice, s));
-        SM_HIP(e, hipMemcpyAsync(S.prefix, prefix.data(), prefix.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.labels, labs.data() + g0, (size_t)ng * sizeof(SmLabel), hipMemcpyHostToDevice, s));
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.prefix, prefix.data(), prefix.size() * sizeof(int), hipMemcpyHostToDevice, s));
         if (elem_bytes == 1) sm_launch_conv_x((const uint8_t*)vol_dev, H, W, S.labels, S.prefix, ng, (int)tiles[0], grmax, S.taps + 0, S.ws, s);
         else if (elem_bytes == 2) sm_launch_conv_x((const uint16_t*)vol_dev, H, W, S.labels, S.prefix, ng, (int)tiles[0], grmax, S.taps + 0, S.ws, s);
         else sm_launch_conv_x((const uint32_t*)vol_dev, H, W, S.labels, S.prefix, ng, (int)tiles[0], grmax, S.taps + 0, S.ws, s);
@@ -365,16 +376,16 @@ static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, i
         else
             hipLaunchKernelGGL((sm_conv_axis_kernel<1, true>), dim3((unsigned)tiles[2]), dim3(256), lds, s, (const SmLabel*)S.labels,
                                (const int*)(S.prefix + 2 * stride), ng, (const float*)S.taps, S.ws, H, W, (uint32_t*)nullptr, (float*)out_dev);
-        SM_HIP(e, hipGetLastError());
-        SM_HIP(e, hipStreamSynchronize(s));                    // the descriptor / prefix host buffers are reused by the next group
+        ENG_HIP_CLEANUP(e, hipGetLastError());
+        ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                    // the descriptor / prefix host buffers are reused by the next group
         g0 = g1;
     }
     if (mode == 0) {
         hipLaunchKernelGGL(sm_cast_kernel, dim3((unsigned)std::min<int64_t>((n / 4 + 255) / 256 + 1, 1 << 16)), dim3(256), 0, s,
                            (const uint32_t*)S.winner, (uint8_t*)out_dev, n);
-        SM_HIP(e, hipGetLastError());
+        ENG_HIP_CLEANUP(e, hipGetLastError());
     }
-    SM_HIP(e, hipStreamSynchronize(s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
     cleanup();
     return SABER_OK;
 }
