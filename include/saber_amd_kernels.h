@@ -8,6 +8,7 @@
  */
 #ifndef SABER_AMD_KERNELS_H
 #define SABER_AMD_KERNELS_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -107,6 +108,15 @@ int saber_k_merge_class_conf(uint16_t* final_labels, float* best, const uint16_t
 /* out (n,H,W) bytes, 1 where bit (x & 31) of bits[n][y][x >> 5] is set: the bool `segmentation` arrays of SAM2AutomaticMaskGenerator's
  * dict list (saber/adapters/sam2/automask.py:50-56 hands them to the segmenters), unpacked before the copy to the host */
 int saber_k_unpack_masks(const uint32_t* bits, int n, int H, int W, uint8_t* out, void* stream);
+/* Hole filling of mask logits (csrc/holefill.hip): upstream's fill_holes_in_mask_scores, which SAM2VideoPredictor applies to the 256 x 256
+ * low-resolution logits after every single-frame inference when fill_hole_area > 0.  Each of the n_planes row-major H x W planes on its own:
+ * background is in[v] <= 0.0f (both zeros are background, NaN and positive values are not), background components are 8-connected, and
+ * out[v] = fill_value where v lies in a background component of at most max_area pixels, else out[v] = in[v] bit for bit.  out may be in.
+ * workspace: device memory of the caller, 4-byte aligned, at least n_planes * H * W * 8 bytes (a uint32 label and a uint32 size per pixel);
+ * a smaller one, max_area < 1, a shape below 1, a null pointer or n_planes * H * W >= 2^31 is an error (-1, saber_k_last_error) and nothing
+ * is written.  Five launches on `stream`; no synchronisation and no allocation inside. */
+int saber_k_fill_holes(const float* in, int n_planes, int H, int W, int max_area, float fill_value, float* out, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* depth-wise Conv2d(k7, p3) of the memory fuser's ConvNeXt blocks; w (C,1,7,7) */
 int saber_k_dwconv7(const float* in, int H, int W, int C, const float* w, const float* b, float* out, void* stream);
 /* the video predictor's mask_downsample: Conv2d(1, 1, k4, s4) */

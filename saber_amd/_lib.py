@@ -146,6 +146,7 @@ SIGNATURES = {
     "saber_k_relabel_frames": (_i, [_vp, _i, C.c_int64, _vp, _i, _vp]),
     "saber_k_merge_max_u16": (_i, [_vp, _vp, C.c_int64, _i, _vp]),
     "saber_k_merge_class_conf": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp]),
+    "saber_k_fill_holes": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, C.c_size_t, _vp]),
     "saber_k_unpack_masks": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "saber_k_dwconv7": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_dwconv7_t": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -20,6 +20,9 @@ class SAM2AdapterConfig(BaseModel):
     cfg: str = Field("small", description="tiny / small / base / large")
     checkpoint: Optional[str] = None
     num_maskmem: int = 2
+    # video path: background components of at most this many pixels of the tracked 256 x 256 mask logits are filled (upstream SAM2's
+    # fill_hole_area; a default upstream build with its CUDA extension uses 8).  None -> SABER_AMD_FILL_HOLE_AREA, else 0 (off)
+    fill_hole_area: Optional[int] = None
     light_modality: bool = False
     amg_cfg: Optional[Any] = None      # cfgAMG instance; None -> cfgAMG() defaults
     min_mask_area: int = 50

@@ -3,6 +3,7 @@
 Hot-path method: segment_image_2d (:48-70) = prep.prepare -> lazily built mask generator -> generate.
 The video-propagation methods of the ABC (set_volume / add_new_mask / propagate_in_video / segment_volume, :76-348) run the memory path
 of saber_amd.adapters.sam2.video on a second engine handle built from config.cfg, like the reference's second model."""
+import os
 from typing import Any, Dict, Iterator, List, Optional, Tuple
 
 import numpy as np
@@ -65,8 +66,14 @@ class SAM2Adapter(BaseAdapter):
             # box or several clicks runs on the handle's 16-bit decoder kernels (16-token route)
             eng = get_engine(self._config.cfg, self.device, self._config.checkpoint, max_images=16, max_prompts=8, replica=1000, multipoint=True)
             W = pretrained_weights.load_weights(self._config.cfg, self._config.checkpoint, video=True)
-            self._video_predictor = VideoPredictor(eng, W, num_maskmem=self._config.num_maskmem)
+            self._video_predictor = VideoPredictor(eng, W, num_maskmem=self._config.num_maskmem, fill_hole_area=self._fill_hole_area())
         return self._video_predictor
+
+    def _fill_hole_area(self) -> int:
+        """config.fill_hole_area, else the environment's SABER_AMD_FILL_HOLE_AREA, else 0 (off; upstream's default build fills holes of up to 8)"""
+        if self._config.fill_hole_area is not None:
+            return int(self._config.fill_hole_area)
+        return int(os.environ.get("SABER_AMD_FILL_HOLE_AREA") or 0)
 
     @torch.inference_mode()
     def set_volume(self, tomogram, offload_video_to_cpu: bool = False) -> None:

@@ -17,7 +17,8 @@ and backwards).  This module is the Python host of that loop; every arithmetic s
 torch is used for device allocation, host<->device copies and a handful of scalar read-backs (argmax of 3 IoU predictions, the sign
 of the object score) - the decisions upstream also takes on the host.  Objects are tracked independently, as upstream does.
 Settings follow the sam2.1 configs and the reference's construction (num_maskmem truncated to SAM2AdapterConfig.num_maskmem = 2,
-predictor.py:28-34); the optional hole-filling CUDA extension of upstream is treated as absent (upstream then skips it with a warning).
+predictor.py:28-34).  Upstream's hole filling (fill_holes_in_mask_scores on the low-resolution logits after every single-frame inference;
+its default fill_hole_area is 8 where its CUDA extension is built) is VideoPredictor(fill_hole_area=...): saber_k_fill_holes, off (0) by default.
 """
 import ctypes as C
 import math
@@ -199,10 +200,17 @@ def load_tomogram_frames_device(tomogram, lib, device, image_size: int = 1024, l
 class VideoPredictor:
     """add_new_mask / propagate_in_video of the SAM2 video predictor on one engine handle."""
 
-    def __init__(self, engine, weights: Dict[str, np.ndarray], num_maskmem: int = 2, batch_objects: Optional[bool] = None, object_batch: int = 16):
+    def __init__(self, engine, weights: Dict[str, np.ndarray], num_maskmem: int = 2, batch_objects: Optional[bool] = None, object_batch: int = 16,
+                 fill_hole_area: int = 0):
         """batch_objects: the memory attention of all objects that are tracked on a frame runs as one set of launches
         (_memory_conditioned_batch; bit-identical to the per-object route); None = the environment switch SABER_AMD_VIDEO_BATCH=1, else off.
-        object_batch: most objects per batch (bounds the workspace and activations: ~0.1 GB per object)"""
+        object_batch: most objects per batch (bounds the workspace and activations: ~0.1 GB per object)
+        fill_hole_area: upstream's setting of the same name (8 in a default upstream build): every 8-connected component of at most that many
+        pixels of the background (logit <= 0) of a frame's 256 x 256 logits is set to the logit 0.1 before the frame's output is stored
+        (_fill_holes).  0 = off: no launch, nothing allocated."""
+        if fill_hole_area < 0:
+            raise ValueError("fill_hole_area must be non-negative")
+        self.fill_hole_area = int(fill_hole_area)
         if num_maskmem > 7:
             raise ValueError("num_maskmem must be at most 7")
         if object_batch < 1:
@@ -267,6 +275,7 @@ class VideoPredictor:
         self._pe1d_cache: Dict[tuple, torch.Tensor] = {}
         self._flash_ws = None
         self._flash_ws_batch = None
+        self._fill_ws = None             # labels + sizes of saber_k_fill_holes
         self._mem_pos_all = None         # mem_pos_t as one (num_maskmem, 4096, 64) table for saber_k_membank_assemble
         self.hook = None
         self.images = None
@@ -468,6 +477,21 @@ class VideoPredictor:
         self._ck(self.lib.saber_k_resize_plane(self._p(x), 1, H, W, self._p(out), Ho, Wo, antialias, post, a, c, self._s()))
         return out
 
+    def _fill_holes(self, low: torch.Tensor) -> torch.Tensor:
+        """upstream fill_holes_in_mask_scores(pred_masks, fill_hole_area) on (..., 256, 256) logits: a new tensor (what has read `low` before
+        keeps the unfilled bits); `low` itself when the step is off"""
+        if self.fill_hole_area <= 0:
+            return low
+        low = low.contiguous()
+        need = low.numel() * 8
+        if self._fill_ws is None or self._fill_ws.numel() < need:
+            self._fill_ws = None
+            self._fill_ws = self._new(need, dtype=torch.uint8)
+        out = torch.empty_like(low)
+        self._ck(self.lib.saber_k_fill_holes(self._p(low), low.numel() // 65536, 256, 256, self.fill_hole_area, 0.1, self._p(out), self._p(self._fill_ws),
+                                             self._fill_ws.numel(), self._s()))
+        return out
+
     # ------------------------------------------------------------------ memory encoder
     def _encode_memory(self, raw: torch.Tensor, mask_for_mem: torch.Tensor, appearing: bool):
         """raw (4096,256) fp32 frame features, mask_for_mem (1024,1024) fp32 already scaled (sigmoid or binary, * 20 - 10).
@@ -522,6 +546,7 @@ class VideoPredictor:
         # the pointer has been through the decoder's own object score (_forward_sam_heads); upstream then blends once more with the
         # appearance the MASK itself says (_use_mask_as_output)
         tok_ptr = ptr if appearing else self.no_obj_ptr_dev
+        low = self._fill_holes(low)
         self.temp[obj_id][frame_idx] = {"pred_masks": low, "obj_ptr": tok_ptr, "obj": 10.0 if appearing else -10.0, "mem": None, "raw": raw}
         return frame_idx, list(self.obj_ids), low
 
@@ -580,6 +605,7 @@ class VideoPredictor:
         else:
             emb = self._memory_conditioned(obj_id, frame_idx, raw, reverse)
         low, obj_v, ptr = self._sam_heads(emb, mask_in, multimask=len(xy) <= 1, slot=self._slot(frame_idx), points=xy, labels=lab)
+        low = self._fill_holes(low)          # stored filled: the preflight's memory mask and a later click's mask prompt see the filled logits
         self.temp[obj_id][frame_idx] = {"pred_masks": low, "obj_ptr": ptr, "obj": obj_v, "mem": None, "raw": raw, "is_cond": is_init}
         return frame_idx, list(self.obj_ids), self._resize(low, 256, 256, Hv, Wv)[None, None]
 
@@ -888,7 +914,7 @@ class VideoPredictor:
         low, obj_v, ptr = self._sam_heads(cond, None, multimask=True, slot=self._slot(t))
         mfm = self._resize(low, 256, 256, 1024, 1024, antialias=0, post=1, a=20.0, c=-10.0)       # sigmoid(high-res logits) * 20 - 10
         mem = self._encode_memory(raw, mfm, obj_v > 0)
-        return {"pred_masks": low, "obj_ptr": ptr, "obj": obj_v, "mem": mem}
+        return {"pred_masks": self._fill_holes(low), "obj_ptr": ptr, "obj": obj_v, "mem": mem}      # filled after the memory encoder, as upstream
 
     def _track_from(self, cond: torch.Tensor, t: int, reverse: bool) -> dict:
         """_track after the memory attention: cond = the object's memory-conditioned features (a row of _memory_conditioned_batch)"""
@@ -896,7 +922,7 @@ class VideoPredictor:
         low, obj_v, ptr = self._sam_heads(cond, None, multimask=True, slot=self._slot(t))
         mfm = self._resize(low, 256, 256, 1024, 1024, antialias=0, post=1, a=20.0, c=-10.0)
         mem = self._encode_memory(raw, mfm, obj_v > 0)
-        return {"pred_masks": low, "obj_ptr": ptr, "obj": obj_v, "mem": mem}
+        return {"pred_masks": self._fill_holes(low), "obj_ptr": ptr, "obj": obj_v, "mem": mem}      # filled after the memory encoder, as upstream
 
     @torch.inference_mode()
     def propagate_in_video(self, start_frame_idx: int, max_frame_num_to_track: Optional[int] = None, reverse: bool = False) -> Iterator:

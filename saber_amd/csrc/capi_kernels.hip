@@ -351,6 +351,11 @@ extern "C" int saber_k_merge_class_conf(uint16_t* final_labels, float* best, con
                                         void* stream) {
     return kcheck(launch_merge_class_conf(final_labels, best, src, cls, conf, L, n, (hipStream_t)stream));
 }
+// hole filling of mask logits (holefill.hip)
+extern "C" int saber_k_fill_holes(const float* in, int n_planes, int H, int W, int max_area, float fill_value, float* out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return kcheck(launch_fill_holes(in, n_planes, H, W, max_area, fill_value, out, workspace, workspace_bytes, (hipStream_t)stream));
+}
 extern "C" int saber_k_add_to_bf16(const float* x, const float* y, int y_rows, uint16_t* out_bf16, float* out_f32, int64_t rows, int C, void* stream) {
     return kcheck(launch_add_to_bf16(x, y, y_rows, out_bf16, out_f32, rows, C, (hipStream_t)stream));
 }

@@ -102,6 +102,10 @@ const char* launch_paint_nearest_stack(const float* logits, int n, int Hv, int W
 const char* launch_relabel_frames(uint16_t* vol, int Z, int64_t HW, const uint16_t* lut, int L, hipStream_t s);
 const char* launch_merge_max_u16(uint16_t* acc, const uint16_t* src, int64_t n, int binarize, hipStream_t s);
 const char* launch_merge_class_conf(uint16_t* fin, float* best, const uint16_t* src, const uint16_t* cls, const float* conf, int L, int64_t n, hipStream_t s);
+// ------------------------------------------------------------------ holefill.hip: small 8-connected background components of n planes -> fill_value
+// workspace: n_planes * H * W * 8 bytes (labels, sizes); out may be in; five launches on s, no synchronisation
+const char* launch_fill_holes(const float* in, int n_planes, int H, int W, int max_area, float fill_value, float* out, void* workspace,
+                              size_t workspace_bytes, hipStream_t s);
 const char* launch_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res,
                                     hipStream_t s);
 const char* launch_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images,

@@ -1,6 +1,6 @@
 """Frames per second of the SAM2 video path: SAM2Adapter.segment_volume on a synthetic tomogram, Hiera-L, seeded weights
 (object-score bias +3 so that the seeded head reports 'present').  One object seeded in the middle slice, forward + backward propagation.
-    python tools/video_bench.py [--frames 32] [--trunk large]
+    python tools/video_bench.py [--frames 32] [--trunk large] [--fill-hole-area 8]
 Prints one JSON line."""
 import argparse
 import json
@@ -14,7 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(trunk="large", frames=32, size=256, reps=2, window=16):
+def run(trunk="large", frames=32, size=256, reps=2, window=16, fill_hole_area=0):
     from saber_amd.adapters.base import SAM2AdapterConfig
     from saber_amd.adapters.sam2.predictor import SAM2Adapter
     from saber_amd.adapters.sam2.video import VideoPredictor
@@ -27,7 +27,7 @@ def run(trunk="large", frames=32, size=256, reps=2, window=16):
     W[k] = W[k] + np.float32(3.0)
     img_keys = set(param_specs(cfg).keys())
     eng = Engine(trunk, device=0, weights={n: v for n, v in W.items() if n in img_keys}, max_images=window, max_prompts=8)
-    vp = VideoPredictor(eng, W, num_maskmem=2)
+    vp = VideoPredictor(eng, W, num_maskmem=2, **({"fill_hole_area": fill_hole_area} if fill_hole_area else {}))
     rng = np.random.default_rng(42)
     tomo = rng.uniform(-1, 1, (frames, size, size)).astype(np.float32)
     yy, xx = np.mgrid[:size, :size]
@@ -47,7 +47,8 @@ def run(trunk="large", frames=32, size=256, reps=2, window=16):
     ad.set_volume(tomo)
     ad.segment_volume(frames // 2, masks=[seed], min_presence_score=0.0)
     prof = eng.profile_end()
-    out = {"what": f"SAM2Adapter.set_volume + segment_volume (host tomogram in, host label volume out), {trunk} trunk, {window} frames per encoder pass, {frames} frames of {size}x{size} (resized to 1024^2), one object, forward + backward",
+    fill = f", holes of up to {fill_hole_area} pixels filled" if fill_hole_area else ""
+    out = {"what": f"SAM2Adapter.set_volume + segment_volume (host tomogram in, host label volume out), {trunk} trunk, {window} frames per encoder pass, {frames} frames of {size}x{size} (resized to 1024^2), one object, forward + backward{fill}",
            "frames_per_s": frames / dt, "ms_per_frame": dt / frames * 1e3, "voxels": int((vol > 0).sum()),
            "engine_kernel_classes_ms_per_frame": {k2: round(v["ms"] / frames, 3) for k2, v in prof.items() if v["launches"]}}
     eng.close()
@@ -58,5 +59,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--trunk", default="large")
+    ap.add_argument("--fill-hole-area", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=2)
     a = ap.parse_args()
-    print(json.dumps(run(a.trunk, a.frames)))
+    print(json.dumps(run(a.trunk, a.frames, reps=a.reps, fill_hole_area=a.fill_hole_area)))
