@@ -9,7 +9,7 @@
 //
 // Arithmetic as in the separate kernels: bf16 MFMA operands (activations rounded where they were rounded before), fp32 accumulation, fp32
 // residual stream / LayerNorm / softmax; the folds multiply the fp32 projections as a bf16 hi + lo pair (two MFMAs), which is closer to
-// dec_fold_kernel's fp32 products than a single bf16 rounding would be.
+// exact product of the fp32 projection with the bf16 weight than a single bf16 rounding would be.
 #include "common.h"
 #include "kernels.h"
 
@@ -29,7 +29,8 @@ __device__ __forceinline__ void fold_operand(const TokCtx& c, const char* F, int
     }
     *hi = pack8(v); *lo = pack8(l);
 }
-// out[p][8 h + t][d] = scale sum_j a[t][16 h + j] W(16 h + j, d), W given TRANSPOSED as WT bf16 [256][128]  (dec_fold_kernel mode 0)
+// out[p][8 h + t][d] = scale sum_j a[t][16 h + j] W(16 h + j, d), W given TRANSPOSED as WT bf16 [256][128]: the folded
+// query / key rows Qt, Kt of decoder_fused.hip's header, head h = 16 consecutive channels of the projection, 8 tokens per head
 // (the wave's 8 weight fragments - 4 head pairs x 2 channel tiles - are loaded once, ahead of the loop over the prompts: fetched inside it
 // they cost one L2 round trip per (prompt, head pair), 16 in a row)
 __device__ __forceinline__ void fold_rows(const TokCtx& c, const char* F, const bf16_t* WT, float scale, bf16_t* out, int p0, int P) {
@@ -57,7 +58,8 @@ __device__ __forceinline__ void fold_rows(const TokCtx& c, const char* F, const 
         }
     }
 }
-// out[p][d][8 h + t] = sum_j a[t][16 h + j] W[d][16 h + j], W bf16 [256][128]  (dec_fold_kernel mode 1: transposed output)
+// out[p][d][8 h + t] = sum_j a[t][16 h + j] W[d][16 h + j], W bf16 [256][128]: the folded values Vt of
+// decoder_fused.hip's header, stored TRANSPOSED (channel d major, the 64 folded columns of a channel contiguous)
 __device__ __forceinline__ void fold_cols(const TokCtx& c, const char* F, const bf16_t* W, int ldw, bf16_t* out, int p0, int P) {
     op16x8 w[4][2];
 #pragma unroll

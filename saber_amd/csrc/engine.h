@@ -109,13 +109,12 @@ struct saber_engine {
     std::vector<char> slot_valid, slot_shared_valid;
 
     // decoder workspace (per chunk of max_prompts prompts)
-    float *tok_pe = nullptr, *queries = nullptr, *tq = nullptr, *tk = nullptr, *tv = nullptr;
-    bf16_t *t_bf0 = nullptr, *t_bf1 = nullptr, *t_att = nullptr, *t_hid = nullptr;
+    float *tok_pe = nullptr, *queries = nullptr, *tq = nullptr, *tk = nullptr;
+    bf16_t* t_att = nullptr;
     bf16_t* keys_bf = nullptr;                                   // image tokens of each prompt [P][4096][256]
     bf16_t *fold_q = nullptr, *fold_k = nullptr, *fold_v = nullptr;  // folded operands [P][64][256]
     float *fold_cb = nullptr, *t2i_part = nullptr, *t2i_ml = nullptr;
-    float *masks4 = nullptr, *hyper_out = nullptr, *iou4 = nullptr, *head_tmp = nullptr;
-    bf16_t *head_bf0 = nullptr, *head_bf1 = nullptr;
+    float *masks4 = nullptr, *hyper_out = nullptr, *iou4 = nullptr;
     int* counts_ws = nullptr;
     float* dec_out_masks = nullptr;  // [max_prompts][3][65536] staging when caller passes NULL
     float* dec_out_iou = nullptr;

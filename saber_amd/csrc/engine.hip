@@ -806,11 +806,7 @@ extern "C" int saber_engine_finalize(saber_engine* e) {
     TRY(eng_alloc(e, &e->queries, P * 8 * 256));
     TRY(eng_alloc(e, &e->tq, P * 8 * 256));
     TRY(eng_alloc(e, &e->tk, P * 8 * 256));
-    TRY(eng_alloc(e, &e->tv, P * 8 * 256));
-    TRY(eng_alloc(e, &e->t_bf0, P * 8 * 256));
-    TRY(eng_alloc(e, &e->t_bf1, P * 8 * 256));
     TRY(eng_alloc(e, &e->t_att, P * 8 * 256));
-    TRY(eng_alloc(e, &e->t_hid, P * 8 * 2048));
     TRY(eng_alloc(e, &e->keys_bf, P * 4096 * 256));
     TRY(eng_alloc(e, &e->h2_bf, P * 4096 * 16));
     TRY(eng_alloc(e, &e->fold_q, P * 64 * 256));
@@ -822,9 +818,6 @@ extern "C" int saber_engine_finalize(saber_engine* e) {
     TRY(eng_alloc(e, &e->masks4, P * 4 * 65536));
     TRY(eng_alloc(e, &e->hyper_out, P * 128));
     TRY(eng_alloc(e, &e->iou4, P * 4));
-    TRY(eng_alloc(e, &e->head_tmp, P * 4));
-    TRY(eng_alloc(e, &e->head_bf0, 4 * P * 256));
-    TRY(eng_alloc(e, &e->head_bf1, 4 * P * 256));
     TRY(eng_alloc(e, &e->counts_ws, 2 * P));
     TRY(eng_alloc(e, &e->dec_out_masks, P * 3 * 65536));
     TRY(eng_alloc(e, &e->dec_out_iou, P * 3));
@@ -1283,96 +1276,10 @@ static int ensure_embb(saber_engine* e, int slot, hipStream_t s) {
     return SABER_OK;
 }
 
-// One chunk of P prompts of K = e->decode_n_pts (2..9) points each on the 16-token route (decoder_t16.hip; saber_engine_set_multipoint): every
-// prompt carries 16 token rows, 7 + K of them real.  The token workspaces sized for max_prompts x 8 rows at finalize hold P <= max_prompts / 2
-// prompts of 16 rows; fold_q / t2i_part / t2i_ml hold the 2P half prompts of the tokens -> image attentions.  Always the fused token side and
-// a materialised X for layer 0 of a mask-prompted decode (no SABER_AMD_NO_TOKFUSE / SABER_AMD_XBUILD / SABER_AMD_FUSE_I2T_T2I variants).
-static int decode_chunk16(saber_engine* e, int slot0, int per_slot, int p_base, const float* pts, const int* labels, int P, int multimask,
-                          const float* mask_in, float mask_clamp, float* out_lowres, float* out_iou, float* out_obj, hipStream_t s,
-                          float* raw4_out, int* out_sel, int mask_in_q0, float prune_iou_thr) {
-    const int K = e->decode_n_pts, nvalid = 7 + K;
-    if (K < 2 || K > 9) return eng_fail(e, SABER_ERR_INVALID, "decode: the 16-token route takes 2..9 points per prompt");
-    if (2 * P > e->max_prompts) return eng_fail(e, SABER_ERR_INVALID, "decode: a 16-token chunk holds at most max_prompts / 2 prompts");
-    const int PT = P * 16;
-    const size_t o256 = (size_t)slot0 * 4096 * 256;
-    const int slot_last = slot0 + (p_base + P - 1) / per_slot;
-    const XMap slots{(int64_t)4096 * 256, per_slot, p_base};
-    const XMap per_prompt{(int64_t)4096 * 256, 1, 0};
-    auto halves = [](XMap m) { return XMap{m.stride, 2 * m.div, 2 * m.off}; };    // half prompt v reads the image tokens of prompt v / 2
-    const float kScale = 0.25f * 1.4426950408889634f;
-    int split = 1;
-    while (split < 8 && 2 * P * split < 512) split *= 2;
-    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_prompt_tokens16(pts, labels, P, K, e->pw, e->tok_pe, s));
-    ENG_HIP(e, hipMemcpyAsync(e->queries, e->tok_pe, sizeof(float) * PT * 256, hipMemcpyDeviceToDevice, s));
-    e->dec_tok_rows = 16;
-    const bf16_t* X;
-    XMap xm;
-    if (mask_in == nullptr) {
-        for (int sl = slot0 + p_base / per_slot; sl <= slot_last; ++sl) TRY(ensure_shared(e, sl, s));
-        X = e->src0_bf + o256; xm = slots;
-    } else {
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, (double)P * (65536.0 * 4 + 4096.0 * 256 * 2), launch_mask_embed_src(mask_in, P, e->emb + o256, slots, e->dense_pe, e->mw, nullptr, e->keys_bf, nullptr, mask_clamp, s, mask_in_q0));
-        X = e->keys_bf; xm = per_prompt;
-    }
-    auto lin = [](const LinW& l) { TokLin t; t.w = l.w; t.b = l.b; t.ldw = l.ldw; t.n = l.out; t.wpk = l.wpk; t.npk = l.wpk_n; return t; };
-    auto lnw = [](const LnW& l) { TokLn t; t.g = l.g; t.b = l.b; return t; };
-    auto base = [&]() { TokSeg g; g.P = P; g.queries = e->queries; g.tok_pe = e->tok_pe; g.kscale = kScale; return g; };
-    auto with_t2i = [&](TokSeg& g, const AttnW& a) { g.do_t2i = 1; g.t2i_q = lin(a.q); g.t2i_kT = a.img_wT; g.tq_out = e->tq; g.fold_q = e->fold_q; };
-    auto with_self = [&](TokSeg& g, const DecLayerW& w, int first) {
-        g.do_self = 1; g.self_first = first; g.sa_q = lin(w.self_attn.q); g.sa_k = lin(w.self_attn.k); g.sa_v = lin(w.self_attn.v); g.sa_o = lin(w.self_attn.o); g.ln1 = lnw(w.n1);
-    };
-    auto with_att_out = [&](TokSeg& g, const AttnW& a, const LnW& ln) { g.t_att = e->t_att; g.att_o = lin(a.o); g.att_ln = lnw(ln); g.att_eps = 1e-5f; };
-    auto with_mlp_i2t = [&](TokSeg& g, const DecLayerW& w) {
-        g.do_mlp = 1; g.mlp1 = lin(w.mlp1); g.mlp2 = lin(w.mlp2); g.mlp1_pk = w.mlp1.wpk; g.mlp2_pk = w.mlp2.wpk; g.ln3 = lnw(w.n3);
-        g.i2t_k = lin(w.i2t.k); g.i2t_v = lin(w.i2t.v); g.i2t_qT = w.i2t.img_wT; g.i2t_qb = w.i2t.q.b; g.i2t_o = w.i2t.o.w;
-        g.tk_out = e->tk; g.fold_k = e->fold_k; g.fold_cb = e->fold_cb; g.fold_v = e->fold_v;
-    };
-    const double tflops = 2.0 * PT * 256.0;
-    auto run_t2i = [&](const AttnW& a) -> int {
-        ENG_KP(e, PC_DEC_T2I, 4.0 * 128 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 4, launch_dec_t2i(X, halves(xm), a.pe_proj, e->fold_q, e->tq, kScale, e->t2i_part, e->t2i_ml, 2 * P, split, a.v.w, a.v.b, e->t_att, s));
-        return SABER_OK;
-    };
-    auto run_i2t = [&](const DecLayerW& w) -> int {
-        ENG_KP(e, PC_DEC_I2T, 4.0 * 128 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 4, launch_dec_i2t16(X, xm, w.i2t.pe_proj, e->fold_k, e->tk, kScale, e->fold_cb, e->fold_v, w.i2t.o.b, w.n4.g, w.n4.b, 1e-5f, e->keys_bf, P, nvalid, s));
-        X = e->keys_bf; xm = per_prompt;
-        return SABER_OK;
-    };
-    {   // S0: self attention of layer 0, operands of its tokens -> image attention
-        TokSeg g = base(); with_self(g, e->dl[0], 1); with_t2i(g, e->dl[0].t2i);
-        ENG_KP(e, PC_DEC_ATTN, tflops * (4 * 256 + 128 + 128), 0.0, launch_dec_tokens16(g, nvalid, s));
-    }
-    TRY(run_t2i(e->dl[0].t2i));
-    {   // S1: rest of layer 0, self attention of layer 1, operands of its tokens -> image attention
-        TokSeg g = base(); with_att_out(g, e->dl[0].t2i, e->dl[0].n2); with_mlp_i2t(g, e->dl[0]); with_self(g, e->dl[1], 0); with_t2i(g, e->dl[1].t2i);
-        ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 4096 + 4 * 128 + 4 * 256 + 256), 0.0, launch_dec_tokens16(g, nvalid, s));
-    }
-    TRY(run_i2t(e->dl[0]));
-    TRY(run_t2i(e->dl[1].t2i));
-    {   // S2: rest of layer 1, operands of the final tokens -> image attention
-        TokSeg g = base(); with_att_out(g, e->dl[1].t2i, e->dl[1].n2); with_mlp_i2t(g, e->dl[1]); with_t2i(g, e->final_attn);
-        ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 4096 + 4 * 128 + 256), 0.0, launch_dec_tokens16(g, nvalid, s));
-    }
-    TRY(run_i2t(e->dl[1]));
-    TRY(run_t2i(e->final_attn));
-    {   // S3: final output projection + LayerNorm, IoU / object-score / hypernetwork heads
-        TokSeg g = base(); with_att_out(g, e->final_attn, e->final_ln);
-        g.do_heads = 1;
-        for (int l = 0; l < 3; ++l) { g.iou[l] = lin(e->iou_head[l]); g.obj[l] = lin(e->obj_head[l]); g.hyper[l] = lin(e->hyper[l]); }
-        g.iou4 = e->iou4; g.obj_out = out_obj; g.hyper_out = e->hyper_out;
-        ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 6 * 512.0 / 16), 0.0, launch_dec_tokens16(g, nvalid, s));
-    }
-    // overflow sentinel, IoU pruning, upscaling and mask selection as on the 8-token route (per prompt: independent of the token count)
-    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_nonfinite_scan(e->iou4, (int64_t)P * 4, e->nonfinite + 1, s));
-    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_nonfinite_scan(e->hyper_out, (int64_t)P * 128, e->nonfinite + 1, s));
-    const uint8_t* live = nullptr;
-    if (prune_iou_thr > 0.f && raw4_out && !multimask && e->iou_prune) {
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_iou_live_flags(e->iou4, P, prune_iou_thr, e->live, e->prune_counters, s));
-        live = e->live;
-    }
-    ENG_KP(e, PC_DEC_UPSCALE, (double)P * 2.0 * (4096.0 * 256 * 256 + 16384.0 * 64 * 128 + 65536.0 * 32 * 4), (double)P * (4096.0 * 256 * 2 + 4 * 65536.0 * 4),
-           launch_dec_upscale(X, e->dc1.w, e->dc1.b, e->up_ln.g, e->up_ln.b, e->dc2p, e->dc2.b, e->fs1 + (size_t)slot0 * 16384 * 64,
-                              e->fs0 + (size_t)slot0 * 65536 * 32, XMap{0, per_slot, p_base}, e->hyper_out, raw4_out ? raw4_out : e->masks4, P, s, live,
-                              e->iou4, multimask, e->nonfinite + 2));
+// Ending of a chunk's decode in every precision mode.  raw4_out: the chunk's 4 low-res planes per prompt stay where they were written
+// (out_iou / out_sel say which to read); otherwise the selected planes are copied to out_lowres.
+static int decode_pick_or_select(saber_engine* e, int P, int multimask, float* out_lowres, float* out_iou, float* raw4_out, int* out_sel, const uint8_t* live,
+                                 hipStream_t s) {
     float* oi = out_iou ? out_iou : e->dec_out_iou;
     if (raw4_out) {
         ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_pick(raw4_out, e->iou4, P, multimask, oi, out_sel, s, live));
@@ -1387,46 +1294,48 @@ static int decode_chunk16(saber_engine* e, int slot0, int per_slot, int p_base, 
 // the chunk reads the features of slot slot0 + (p_base + p) / per_slot.
 // raw4_out: the chunk's 4 low-res planes per prompt are written there and stay (no selection copy: out_iou / out_sel say which to read);
 // mask_in_q0 >= 0: mask_in is the raw 4-plane output of a multimask decode, this chunk's first prompt refines global candidate mask_in_q0
+//
+// The 16-bit body serves two routes that differ in the token rows R a prompt carries.  R = 8: one point per prompt, [obj, iou, mask0..3, point,
+// pad] (decoder_tokens.hip).  R = 16: K = e->decode_n_pts (2..9) points per prompt, nvalid = 7 + K of the 16 rows real (decoder_t16.hip;
+// saber_engine_set_multipoint).  The token workspaces sized for max_prompts x 8 rows at finalize then hold P <= max_prompts / 2 prompts, and the
+// tokens -> image attention, whose kernel takes 8 query tokens, runs over the nh * P half prompts of nh = R / 8 (fold_q / t2i_part / t2i_ml hold them).
 static int decode_chunk(saber_engine* e, int slot0, int per_slot, int p_base, const float* pts, const int* labels, int P, int multimask,
                         const float* mask_in, float mask_clamp, float* out_lowres, float* out_iou, float* out_obj, hipStream_t s,
                         float* raw4_out = nullptr, int* out_sel = nullptr, int mask_in_q0 = -1, float prune_iou_thr = 0.f) {
     if (e->precision == SABER_PRECISION_EXACT) {
-        float* m4 = raw4_out ? raw4_out : e->masks4;
-        TRY(exact_decode_core(e, slot0, per_slot, p_base, pts, labels, P, mask_in, mask_clamp, mask_in_q0, out_obj, m4, s, e->decode_n_pts));
-        float* oi = out_iou ? out_iou : e->dec_out_iou;
-        if (raw4_out) { ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_pick(raw4_out, e->iou4, P, multimask, oi, out_sel, s)); return SABER_OK; }
-        float* om = out_lowres ? out_lowres : e->dec_out_masks;
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_select(e->masks4, e->iou4, P, multimask, om, oi, e->counts_ws, s));
-        return SABER_OK;
+        TRY(exact_decode_core(e, slot0, per_slot, p_base, pts, labels, P, mask_in, mask_clamp, mask_in_q0, out_obj, raw4_out ? raw4_out : e->masks4, s, e->decode_n_pts));
+        return decode_pick_or_select(e, P, multimask, out_lowres, out_iou, raw4_out, out_sel, nullptr, s);
     }
-    if (e->decode_n_pts != 1) {
-        if (e->multipoint)
-            return decode_chunk16(e, slot0, per_slot, p_base, pts, labels, P, multimask, mask_in, mask_clamp, out_lowres, out_iou, out_obj, s, raw4_out, out_sel,
-                                  mask_in_q0, prune_iou_thr);
+    const int K = e->decode_n_pts;
+    if (K != 1 && !e->multipoint)
         return eng_fail(e, SABER_ERR_STATE, "prompts of several points (clicks, boxes) are decoded in the exact precision mode only: the bf16 kernels are built for 8 decoder tokens per prompt");
+    const int R = K != 1 ? 16 : 8, nh = R / 8, nvalid = 7 + K;       // nvalid: read on the 16-row route only
+    if (R == 16) {
+        if (K < 2 || K > 9) return eng_fail(e, SABER_ERR_INVALID, "decode: the 16-token route takes 2..9 points per prompt");
+        if (2 * P > e->max_prompts) return eng_fail(e, SABER_ERR_INVALID, "decode: a 16-token chunk holds at most max_prompts / 2 prompts");
     }
-    const int T = 8;
-    const int PT = P * T;
+    const int PT = P * R;
     const size_t o256 = (size_t)slot0 * 4096 * 256;
-    const bool shared = (mask_in == nullptr);
     const int slot_last = slot0 + (p_base + P - 1) / per_slot;
     const XMap slots{(int64_t)4096 * 256, per_slot, p_base};          // per-slot tensors of 4096 x 256 elements
     const XMap per_prompt{(int64_t)4096 * 256, 1, 0};
     const float kScale = 0.25f * 1.4426950408889634f;  // head_dim 16 ^ -0.5 * log2(e): scores live in the exp2 domain
     int split = 1;
-    while (split < 8 && P * split < 512) split *= 2;
-    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_prompt_tokens(pts, labels, P, e->pw, e->tok_pe, s));
+    while (split < 8 && nh * P * split < 512) split *= 2;
+    if (R == 16) ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_prompt_tokens16(pts, labels, P, K, e->pw, e->tok_pe, s));
+    else ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_prompt_tokens(pts, labels, P, e->pw, e->tok_pe, s));
     ENG_HIP(e, hipMemcpyAsync(e->queries, e->tok_pe, sizeof(float) * PT * 256, hipMemcpyDeviceToDevice, s));
+    e->dec_tok_rows = R;
     const bf16_t* X;      // image tokens of each prompt, bf16 [4096][256], engine order
     XMap xm;
     XBuild xb;
     const XBuild* build = nullptr;          // layer 0 of a mask-prompted decode: X0 tiles assembled in the kernels
-    // Opt-in experiment (round 3, SABER_AMD_XBUILD=1, read per call): assemble the m2m prompts' src inside layer 0's dec_t2i / dec_i2t instead
-    // of materialising it.  Bit-identical and 55 GB per slice less HBM traffic, but SLOWER on this memory system: the fp32 image_embed
+    // Opt-in experiment (round 3, SABER_AMD_XBUILD=1, read per call, 8-row route only): assemble the m2m prompts' src inside layer 0's dec_t2i /
+    // dec_i2t instead of materialising it.  Bit-identical and 55 GB per slice less HBM traffic, but SLOWER on this memory system: the fp32 image_embed
     // tiles (4 MB per prompt and pass, from the Infinity Cache) cost more than the 2 MB of bf16 src from HBM they replace, and with two
     // slices in flight they evict the encoder's working set from that cache (same-box A/B: 156.7 vs 144.3 ms per slice).  DESIGN.md section 4.
-    const bool no_build = getenv("SABER_AMD_XBUILD") == nullptr;
-    if (shared) {
+    const bool no_build = R == 16 || getenv("SABER_AMD_XBUILD") == nullptr;
+    if (mask_in == nullptr) {
         for (int sl = slot0 + p_base / per_slot; sl <= slot_last; ++sl) TRY(ensure_shared(e, sl, s));
         X = e->src0_bf + o256; xm = slots;
     } else if (no_build) {
@@ -1442,141 +1351,62 @@ static int decode_chunk(saber_engine* e, int slot0, int per_slot, int p_base, co
         X = nullptr; xm = per_prompt;
     }
 
-    static const bool no_tokfuse = getenv("SABER_AMD_NO_TOKFUSE") != nullptr;      // development A/B switch: the ~58 separate token-side launches
-    if (!no_tokfuse) {
-        // token side as four fused segments (decoder_tokens.hip) around the five image-side kernels
-        auto lin = [](const LinW& l) { TokLin t; t.w = l.w; t.b = l.b; t.ldw = l.ldw; t.n = l.out; t.wpk = l.wpk; t.npk = l.wpk_n; return t; };
-        auto lnw = [](const LnW& l) { TokLn t; t.g = l.g; t.b = l.b; return t; };
-        auto base = [&]() { TokSeg g; g.P = P; g.queries = e->queries; g.tok_pe = e->tok_pe; g.kscale = kScale; return g; };
-        auto with_t2i = [&](TokSeg& g, const AttnW& a) { g.do_t2i = 1; g.t2i_q = lin(a.q); g.t2i_kT = a.img_wT; g.tq_out = e->tq; g.fold_q = e->fold_q; };
-        auto with_self = [&](TokSeg& g, const DecLayerW& w, int first) {
-            g.do_self = 1; g.self_first = first; g.sa_q = lin(w.self_attn.q); g.sa_k = lin(w.self_attn.k); g.sa_v = lin(w.self_attn.v); g.sa_o = lin(w.self_attn.o); g.ln1 = lnw(w.n1);
-        };
-        auto with_att_out = [&](TokSeg& g, const AttnW& a, const LnW& ln) { g.t_att = e->t_att; g.att_o = lin(a.o); g.att_ln = lnw(ln); g.att_eps = 1e-5f; };
-        auto with_mlp_i2t = [&](TokSeg& g, const DecLayerW& w) {
-            g.do_mlp = 1; g.mlp1 = lin(w.mlp1); g.mlp2 = lin(w.mlp2); g.mlp1_pk = w.mlp1.wpk; g.mlp2_pk = w.mlp2.wpk; g.ln3 = lnw(w.n3);
-            g.i2t_k = lin(w.i2t.k); g.i2t_v = lin(w.i2t.v); g.i2t_qT = w.i2t.img_wT; g.i2t_qb = w.i2t.q.b; g.i2t_o = w.i2t.o.w;
-            g.tk_out = e->tk; g.fold_k = e->fold_k; g.fold_cb = e->fold_cb; g.fold_v = e->fold_v;
-        };
-        const double tflops = 2.0 * PT * 256.0;     // per 256 x 1 column of weights
-        auto run_t2i = [&](const AttnW& a) -> int {
-            ENG_KP(e, PC_DEC_T2I, 4.0 * 64 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 2, launch_dec_t2i(X, xm, a.pe_proj, e->fold_q, e->tq, kScale, e->t2i_part, e->t2i_ml, P, split, a.v.w, a.v.b, e->t_att, s, build));
-            return SABER_OK;
-        };
-        auto run_i2t = [&](const DecLayerW& w) -> int {
-            ENG_KP(e, PC_DEC_I2T, 4.0 * 64 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 4, launch_dec_i2t(X, xm, w.i2t.pe_proj, e->fold_k, e->tk, kScale, e->fold_cb, e->fold_v, w.i2t.o.b, w.n4.g, w.n4.b, 1e-5f, e->keys_bf, P, s, build));
-            X = e->keys_bf; xm = per_prompt; build = nullptr;
-            return SABER_OK;
-        };
-        // Opt-in (round 5, SABER_AMD_FUSE_I2T_T2I=1, read per call): image -> tokens of a layer and the tokens -> image attention that follows
-        // it in ONE kernel (dec_i2t_t2i_kernel: X' is the next attention's key / value block while it is still in LDS).  Same results as the
-        // two launches up to the order of the online softmax; measured slower (one wave per SIMD): DESIGN.md section 8.2.
-        const bool fuse = getenv("SABER_AMD_FUSE_I2T_T2I") != nullptr && P >= 128;
-        auto run_i2t_t2i = [&](const DecLayerW& w, const AttnW& a) -> int {
-            if (!fuse || build != nullptr) { TRY(run_i2t(w)); return run_t2i(a); }
-            ENG_KP(e, PC_DEC_I2T, 8.0 * 64 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 4,
-                   launch_dec_i2t_t2i(X, xm, w.i2t.pe_proj, e->fold_k, e->tk, kScale, e->fold_cb, e->fold_v, w.i2t.o.b, w.n4.g, w.n4.b, 1e-5f, e->keys_bf, P,
-                                      a.pe_proj, e->fold_q, e->tq, kScale, a.v.w, a.v.b, e->t_att, s));
-            X = e->keys_bf; xm = per_prompt; build = nullptr;
-            return SABER_OK;
-        };
-        {   // S0: self attention of layer 0, operands of its tokens -> image attention
-            TokSeg g = base(); with_self(g, e->dl[0], 1); with_t2i(g, e->dl[0].t2i);
-            ENG_KP(e, PC_DEC_ATTN, tflops * (4 * 256 + 128 + 128), 0.0, launch_dec_tokens(g, s));
-        }
-        TRY(run_t2i(e->dl[0].t2i));
-        {   // S1: rest of layer 0 on the token side, self attention of layer 1, operands of its tokens -> image attention
-            TokSeg g = base(); with_att_out(g, e->dl[0].t2i, e->dl[0].n2); with_mlp_i2t(g, e->dl[0]); with_self(g, e->dl[1], 0); with_t2i(g, e->dl[1].t2i);
-            ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 4096 + 4 * 128 + 4 * 256 + 256), 0.0, launch_dec_tokens(g, s));
-        }
-        TRY(run_i2t_t2i(e->dl[0], e->dl[1].t2i));
-        {   // S2: rest of layer 1, operands of the final tokens -> image attention
-            TokSeg g = base(); with_att_out(g, e->dl[1].t2i, e->dl[1].n2); with_mlp_i2t(g, e->dl[1]); with_t2i(g, e->final_attn);
-            ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 4096 + 4 * 128 + 256), 0.0, launch_dec_tokens(g, s));
-        }
-        TRY(run_i2t_t2i(e->dl[1], e->final_attn));
-        {   // S3: final output projection + LayerNorm, IoU / object-score / hypernetwork heads
-            TokSeg g = base(); with_att_out(g, e->final_attn, e->final_ln);
-            g.do_heads = 1;
-            for (int l = 0; l < 3; ++l) { g.iou[l] = lin(e->iou_head[l]); g.obj[l] = lin(e->obj_head[l]); g.hyper[l] = lin(e->hyper[l]); }
-            g.iou4 = e->iou4; g.obj_out = out_obj; g.hyper_out = e->hyper_out;
-            ENG_KP(e, PC_DEC_ATTN, tflops * (128 + 6 * 512.0 / 8), 0.0, launch_dec_tokens(g, s));
-        }
-    } else {
-    // tokens -> image: fold q into 64 rows of dimension 256, stream X once (dec_t2i), un-fold with v_proj
-    auto t2i = [&](const AttnW& a, const LnW& ln) -> int {
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_add_to_bf16(e->queries, e->tok_pe, PT, e->t_bf0, nullptr, PT, 256, s));
-        GemmParams g = mk_gemm(e->t_bf0, 256, PT, a.q);
-        g.Cf = e->tq; g.ldcf = 128;
-        ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_dec_fold(e->tq, a.k.w, nullptr, 0, kScale, e->fold_q, nullptr, P, s));
-        ENG_KP(e, PC_DEC_T2I, 4.0 * 64 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 2, launch_dec_t2i(X, xm, a.pe_proj, e->fold_q, e->tq, kScale, e->t2i_part, e->t2i_ml, P, split, a.v.w, a.v.b, e->t_att, s, build));
-        g = mk_gemm(e->t_att, 128, PT, a.o);
-        g.Cf = e->queries; g.ldcf = 256; g.res = e->queries; g.ldres = 256;
-        ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        ENG_KP(e, PC_LAYERNORM, 0.0, 0.0, ln_run(e->queries, ln, 1e-5f, PT, 256, e->queries, nullptr, ACT_NONE, s));
+    // token side as four fused segments (decoder_tokens.hip / decoder_t16.hip) around the five image-side kernels
+    auto lin = [](const LinW& l) { TokLin t; t.w = l.w; t.b = l.b; t.ldw = l.ldw; t.n = l.out; t.wpk = l.wpk; t.npk = l.wpk_n; return t; };
+    auto lnw = [](const LnW& l) { TokLn t; t.g = l.g; t.b = l.b; return t; };
+    auto base = [&]() { TokSeg g; g.P = P; g.queries = e->queries; g.tok_pe = e->tok_pe; g.kscale = kScale; return g; };
+    auto with_t2i = [&](TokSeg& g, const AttnW& a) { g.do_t2i = 1; g.t2i_q = lin(a.q); g.t2i_kT = a.img_wT; g.tq_out = e->tq; g.fold_q = e->fold_q; };
+    auto with_self = [&](TokSeg& g, const DecLayerW& w, int first) {
+        g.do_self = 1; g.self_first = first; g.sa_q = lin(w.self_attn.q); g.sa_k = lin(w.self_attn.k); g.sa_v = lin(w.self_attn.v); g.sa_o = lin(w.self_attn.o); g.ln1 = lnw(w.n1);
+    };
+    auto with_att_out = [&](TokSeg& g, const AttnW& a, const LnW& ln) { g.t_att = e->t_att; g.att_o = lin(a.o); g.att_ln = lnw(ln); g.att_eps = 1e-5f; };
+    auto with_mlp_i2t = [&](TokSeg& g, const DecLayerW& w) {
+        g.do_mlp = 1; g.mlp1 = lin(w.mlp1); g.mlp2 = lin(w.mlp2); g.mlp1_pk = w.mlp1.wpk; g.mlp2_pk = w.mlp2.wpk; g.ln3 = lnw(w.n3);
+        g.i2t_k = lin(w.i2t.k); g.i2t_v = lin(w.i2t.v); g.i2t_qT = w.i2t.img_wT; g.i2t_qb = w.i2t.q.b; g.i2t_o = w.i2t.o.w;
+        g.tk_out = e->tk; g.fold_k = e->fold_k; g.fold_cb = e->fold_cb; g.fold_v = e->fold_v;
+    };
+    const double tflops = 2.0 * PT * 256.0;     // per 256 x 1 column of weights
+    const double xflops = 4.0 * (8 * R) * 4096.0 * 256 * P;      // a cross attention: 8 R folded rows over the 4096 x 256 image tokens of P prompts
+    auto run_tokens = [&](const TokSeg& g, double cols) -> int {
+        if (R == 16) ENG_KP(e, PC_DEC_ATTN, tflops * cols, 0.0, launch_dec_tokens16(g, nvalid, s));
+        else ENG_KP(e, PC_DEC_ATTN, tflops * cols, 0.0, launch_dec_tokens(g, s));
         return SABER_OK;
     };
-
-    for (int l = 0; l < 2; ++l) {
-        const DecLayerW& w = e->dl[l];
-        // (1) self attention of the tokens
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_add_to_bf16(e->queries, l == 0 ? nullptr : e->tok_pe, PT, e->t_bf0, nullptr, PT, 256, s));
-        const bf16_t* vin = e->t_bf0;
-        if (l > 0) { ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_add_to_bf16(e->queries, nullptr, 1, e->t_bf1, nullptr, PT, 256, s)); vin = e->t_bf1; }
-        GemmParams g = mk_gemm(e->t_bf0, 256, PT, w.self_attn.q); g.Cf = e->tq; g.ldcf = 256; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(e->t_bf0, 256, PT, w.self_attn.k); g.Cf = e->tk; g.ldcf = 256; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(vin, 256, PT, w.self_attn.v); g.Cf = e->tv; g.ldcf = 256; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        ENG_KP(e, PC_DEC_ATTN, 0.0, 0.0, launch_dec_attention(e->tq, e->tk, e->tv, e->t_att, P, T, T, 8, 32, T * 256, T * 256, T * 256, T * 256, s));
-        g = mk_gemm(e->t_att, 256, PT, w.self_attn.o);
-        g.Cf = e->queries; g.ldcf = 256;
-        if (l > 0) { g.res = e->queries; g.ldres = 256; }
-        ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        ENG_KP(e, PC_LAYERNORM, 0.0, 0.0, ln_run(e->queries, w.n1, 1e-5f, PT, 256, e->queries, nullptr, ACT_NONE, s));
-        // (2) tokens -> image
-        TRY(t2i(w.t2i, w.n2));
-        // (3) MLP
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_add_to_bf16(e->queries, nullptr, 1, e->t_bf0, nullptr, PT, 256, s));
-        g = mk_gemm(e->t_bf0, 256, PT, w.mlp1); g.Cb = e->t_hid; g.ldcb = 2048; g.act = ACT_RELU; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(e->t_hid, 2048, PT, w.mlp2); g.Cf = e->queries; g.ldcf = 256; g.res = e->queries; g.ldres = 256; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        ENG_KP(e, PC_LAYERNORM, 0.0, 0.0, ln_run(e->queries, w.n3, 1e-5f, PT, 256, e->queries, nullptr, ACT_NONE, s));
-        // (4) image -> tokens, fused with the residual and norm4: X <- LN(X + attn)
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_add_to_bf16(e->queries, e->tok_pe, PT, e->t_bf0, nullptr, PT, 256, s));
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_add_to_bf16(e->queries, nullptr, 1, e->t_bf1, nullptr, PT, 256, s));
-        g = mk_gemm(e->t_bf0, 256, PT, w.i2t.k); g.Cf = e->tk; g.ldcf = 128; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(e->t_bf1, 256, PT, w.i2t.v); g.Cf = e->tv; g.ldcf = 128; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_dec_fold(e->tk, w.i2t.q.w, w.i2t.q.b, 0, kScale, e->fold_k, e->fold_cb, P, s));
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_dec_fold(e->tv, w.i2t.o.w, nullptr, 1, 1.0f, e->fold_v, nullptr, P, s));
-        ENG_KP(e, PC_DEC_I2T, 4.0 * 64 * 4096.0 * 256 * P, (double)P * 4096 * 256 * 4, launch_dec_i2t(X, xm, w.i2t.pe_proj, e->fold_k, e->tk, kScale, e->fold_cb, e->fold_v, w.i2t.o.b, w.n4.g, w.n4.b, 1e-5f, e->keys_bf, P, s, build));
+    auto run_t2i = [&](const AttnW& a) -> int {       // half prompt v reads the image tokens of prompt v / nh
+        ENG_KP(e, PC_DEC_T2I, xflops, (double)P * 4096 * 256 * 2 * nh,
+               launch_dec_t2i(X, XMap{xm.stride, nh * xm.div, nh * xm.off}, a.pe_proj, e->fold_q, e->tq, kScale, e->t2i_part, e->t2i_ml, nh * P, split, a.v.w, a.v.b, e->t_att, s, build));
+        return SABER_OK;
+    };
+    auto run_i2t = [&](const DecLayerW& w) -> int {
+        if (R == 16) ENG_KP(e, PC_DEC_I2T, xflops, (double)P * 4096 * 256 * 4, launch_dec_i2t16(X, xm, w.i2t.pe_proj, e->fold_k, e->tk, kScale, e->fold_cb, e->fold_v, w.i2t.o.b, w.n4.g, w.n4.b, 1e-5f, e->keys_bf, P, nvalid, s));
+        else ENG_KP(e, PC_DEC_I2T, xflops, (double)P * 4096 * 256 * 4, launch_dec_i2t(X, xm, w.i2t.pe_proj, e->fold_k, e->tk, kScale, e->fold_cb, e->fold_v, w.i2t.o.b, w.n4.g, w.n4.b, 1e-5f, e->keys_bf, P, s, build));
         X = e->keys_bf; xm = per_prompt; build = nullptr;
-    }
-    TRY(t2i(e->final_attn, e->final_ln));
-
-    // heads
-    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_add_to_bf16(e->queries, nullptr, 1, e->t_bf0, nullptr, PT, 256, s));
-    auto mlp3 = [&](const LinW* L, const bf16_t* A, int last_act, float* outf, int ldo) -> int {
-        GemmParams g = mk_gemm(A, T * 256, P, L[0]); g.Cb = e->head_bf0; g.ldcb = 256; g.act = ACT_RELU; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(e->head_bf0, 256, P, L[1]); g.Cb = e->head_bf1; g.ldcb = 256; g.act = ACT_RELU; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(e->head_bf1, 256, P, L[2]); g.Cf = outf; g.ldcf = ldo; g.act = last_act; ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K, gemm_bytes(g), launch_gemm(g, s));
         return SABER_OK;
     };
-    TRY(mlp3(e->iou_head, e->t_bf0 + 1 * 256, ACT_SIGMOID, e->iou4, 4));
-    if (out_obj) TRY(mlp3(e->obj_head, e->t_bf0, ACT_NONE, out_obj, 1));
-    {   // 4 hypernetwork MLPs as batched GEMMs (batch = mask token)
-        GemmParams g = mk_gemm(e->t_bf0 + 2 * 256, T * 256, P, e->hyper[0]);
-        g.batch = 4; g.strideA = 256; g.strideW = 256 * 256; g.strideBias = 256;
-        g.Cb = e->head_bf0; g.ldcb = 256; g.strideCb = (int64_t)P * 256; g.act = ACT_RELU;
-        ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K * 4, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(e->head_bf0, 256, P, e->hyper[1]);
-        g.batch = 4; g.strideA = (int64_t)P * 256; g.strideW = 256 * 256; g.strideBias = 256;
-        g.Cb = e->head_bf1; g.ldcb = 256; g.strideCb = (int64_t)P * 256; g.act = ACT_RELU;
-        ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K * 4, gemm_bytes(g), launch_gemm(g, s));
-        g = mk_gemm(e->head_bf1, 256, P, e->hyper[2]);
-        g.batch = 4; g.strideA = (int64_t)P * 256; g.strideW = 32 * 256; g.strideBias = 32;
-        g.Cf = e->hyper_out; g.ldcf = 128; g.strideCf = 32;
-        ENG_KP(e, PC_GEMM, 2.0 * g.M * (double)g.N * g.K * 4, gemm_bytes(g), launch_gemm(g, s));
+    {   // S0: self attention of layer 0, operands of its tokens -> image attention
+        TokSeg g = base(); with_self(g, e->dl[0], 1); with_t2i(g, e->dl[0].t2i);
+        TRY(run_tokens(g, 4 * 256 + 128 + 128));
     }
-    }   // (separate token-side launches)
+    TRY(run_t2i(e->dl[0].t2i));
+    {   // S1: rest of layer 0 on the token side, self attention of layer 1, operands of its tokens -> image attention
+        TokSeg g = base(); with_att_out(g, e->dl[0].t2i, e->dl[0].n2); with_mlp_i2t(g, e->dl[0]); with_self(g, e->dl[1], 0); with_t2i(g, e->dl[1].t2i);
+        TRY(run_tokens(g, 128 + 4096 + 4 * 128 + 4 * 256 + 256));
+    }
+    TRY(run_i2t(e->dl[0]));
+    TRY(run_t2i(e->dl[1].t2i));
+    {   // S2: rest of layer 1, operands of the final tokens -> image attention
+        TokSeg g = base(); with_att_out(g, e->dl[1].t2i, e->dl[1].n2); with_mlp_i2t(g, e->dl[1]); with_t2i(g, e->final_attn);
+        TRY(run_tokens(g, 128 + 4096 + 4 * 128 + 256));
+    }
+    TRY(run_i2t(e->dl[1]));
+    TRY(run_t2i(e->final_attn));
+    {   // S3: final output projection + LayerNorm, IoU / object-score / hypernetwork heads
+        TokSeg g = base(); with_att_out(g, e->final_attn, e->final_ln);
+        g.do_heads = 1;
+        for (int l = 0; l < 3; ++l) { g.iou[l] = lin(e->iou_head[l]); g.obj[l] = lin(e->obj_head[l]); g.hyper[l] = lin(e->hyper[l]); }
+        g.iou4 = e->iou4; g.obj_out = out_obj; g.hyper_out = e->hyper_out;
+        TRY(run_tokens(g, 128 + 6 * 512.0 / R));
+    }
     // sentinel: every token-side quantity of the batch ends in the predicted IoUs and the hypernetwork outputs (a NaN / inf row of the image-token
     // state reaches them through the tokens -> image attentions: its score is NaN, so is the softmax sum); the logits are checked where they are stored
     ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_nonfinite_scan(e->iou4, (int64_t)P * 4, e->nonfinite + 1, s));
@@ -1588,19 +1418,12 @@ static int decode_chunk(saber_engine* e, int slot0, int per_slot, int p_base, co
         ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_iou_live_flags(e->iou4, P, prune_iou_thr, e->live, e->prune_counters, s));
         live = e->live;
     }
-    // upscaling head fused with the hypernetwork product (dec_upscale_kernel)
+    // upscaling head fused with the hypernetwork product (dec_upscale_kernel); per prompt, independent of the token count
     ENG_KP(e, PC_DEC_UPSCALE, (double)P * 2.0 * (4096.0 * 256 * 256 + 16384.0 * 64 * 128 + 65536.0 * 32 * 4), (double)P * (4096.0 * 256 * 2 + 4 * 65536.0 * 4),
            launch_dec_upscale(X, e->dc1.w, e->dc1.b, e->up_ln.g, e->up_ln.b, e->dc2p, e->dc2.b, e->fs1 + (size_t)slot0 * 16384 * 64,
                               e->fs0 + (size_t)slot0 * 65536 * 32, XMap{0, per_slot, p_base}, e->hyper_out, raw4_out ? raw4_out : e->masks4, P, s, live,
                               getenv("SABER_AMD_ALL_PLANES") ? nullptr : e->iou4, multimask, e->nonfinite + 2));      // (development A/B: all four planes)
-    float* oi = out_iou ? out_iou : e->dec_out_iou;
-    if (raw4_out) {
-        ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_pick(raw4_out, e->iou4, P, multimask, oi, out_sel, s, live));
-        return SABER_OK;
-    }
-    float* om = out_lowres ? out_lowres : e->dec_out_masks;
-    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_mask_select(e->masks4, e->iou4, P, multimask, om, oi, e->counts_ws, s));
-    return SABER_OK;
+    return decode_pick_or_select(e, P, multimask, out_lowres, out_iou, raw4_out, out_sel, live, s);
 }
 
 int eng_decode(saber_engine* e, int slot, int per_slot, const float* pts_dev, const int* labels_dev, int n, int multimask,

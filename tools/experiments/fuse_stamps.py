@@ -1,7 +1,8 @@
-"""In-kernel cycle stamps of the fused dec_i2t_t2i kernel through the engine (development): python tools/fuse_stamps.py [P]
+"""In-kernel cycle stamps of the parked fused dec_i2t_t2i kernel (dec_i2t_t2i.hip, revived as README.md says) through the engine:
+python tools/experiments/fuse_stamps.py [P]
 The stamp buffer is shared by every stamp-aware kernel of the decode; the fused kernel of layer 1 + final attention is the last writer."""
 import ctypes as C, sys, os
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ["SABER_AMD_FUSE_I2T_T2I"] = "1"
 import torch
 from saber_amd import _lib

@@ -1,11 +1,11 @@
-"""A/B of an opt-in decoder kernel on the decode of P prompts: python tools/fuse_ab.py [P] [ENV]  (ENV = SABER_AMD_FUSE_I2T_T2I (default) or
-SABER_AMD_T2I_W1 / SABER_AMD_I2T_W1 (default on: A/B is =0 against unset); per-class profile, ms per decode)"""
+"""A/B of an opt-in decoder kernel on the decode of P prompts: python tools/fuse_ab.py [P] [ENV]  (ENV = SABER_AMD_T2I_W1 (default) or
+SABER_AMD_I2T_W1: default on, the A/B is =0 against unset; any other switch: =1 against unset; per-class profile, ms per decode)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from saber_amd.engine import Engine
 P = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-ENV = sys.argv[2] if len(sys.argv) > 2 else "SABER_AMD_FUSE_I2T_T2I"
+ENV = sys.argv[2] if len(sys.argv) > 2 else "SABER_AMD_T2I_W1"
 eng = Engine("large", device=0, seed=0, max_images=1, max_prompts=1024)
 eng.encode(torch.rand(1024, 1024, device="cuda"))
 pts = torch.rand(P, 2, device="cuda") * 1024
