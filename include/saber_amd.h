@@ -204,7 +204,8 @@ int saber_engine_set_precision(saber_engine* e, int precision);
  * accumulators, the fp32 residual stream and every LayerNorm / softmax statistic carry it (as inf or NaN) into (a) the three feature maps of
  * the encoder pass, (b) the decoder batch's predicted IoUs / hypernetwork outputs and (c) the low-res logits.  The engine counts non-finite
  * values there on the device, on the caller's stream: one HBM-bound scan of the feature maps per encoder pass (16 MB per crop), two tiny
- * scans per decoder batch, one fma per stored pixel inside dec_upscale.  saber_amg_generate reads the counters with the records at its one
+ * scans per decoder batch (the one over the hypernetwork outputs inside the kernel that packs them for dec_upscale), one fma per stored
+ * pixel inside dec_upscale.  saber_amg_generate reads the counters with the records at its one
  * synchronisation and returns SABER_ERR_RANGE (nothing of that call's output may be used).  After saber_encode / saber_decode_points /
  * saber_decode_prompts (asynchronous, no synchronisation inside) call saber_engine_check_finite where the host synchronises anyway: it
  * waits for `stream`, returns SABER_ERR_RANGE with a message naming the stage when any counter is non-zero, and clears the counters.

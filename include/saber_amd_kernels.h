@@ -243,6 +243,12 @@ int saber_k_dec_t2i(const uint16_t* X, int64_t x_batch_stride, const uint16_t* p
 int saber_k_dec_upscale(const uint16_t* X, const float* w0, const float* b0, const float* ln_gamma, const float* ln_beta, const float* w3, const float* b3,
                         const float* fs1, const float* fs0, int slot_div, int slot_off, const float* hyper, float* masks4, int P, const uint8_t* live,
                         const float* iou4, int multimask, unsigned int* sentinel, void* stream);
+/* The hypernetwork operand as dec_upscale_kernel reads it (the engine runs this once per decoded batch; saber_k_dec_upscale runs it on its fp32 hyper):
+ * out [P][2][4][4][8] in the operand type (512 B per prompt) = hyper [P][4][32] f32 split into hi = round(v) (half 0) and lo = round(v - hi) (half 1);
+ * element [m][fg][j] is channel 4 fg + j (j < 4) or 16 + 4 fg + (j - 4) of hyper[p][m][.], the k-slot order of the hypernetwork MFMA.  Both 16-byte aligned.
+ * nonfinite_counter (optional): += the number of scanning lanes that met a NaN / inf in hyper, the count of the engine's overflow sentinel over
+ * the same 128 P values (a lane scans groups of four consecutive values: one group each up to P = 8, up to eight beyond; > 0 = something overflowed). */
+int saber_k_hyper_pack(const float* hyper, int P, uint16_t* out, unsigned int* nonfinite_counter, void* stream);
 /* The selection among the four planes (reference: MaskDecoder.forward / _dynamic_multimask_via_stability, delta 0.05, threshold 0.98), fp32:
  * multimask: out_iou [P][3] = iou4[:, 1:], out_sel untouched.  Single mask: stability = #(plane 0 > 0.05) / #(plane 0 > -0.05) in fp32 (1 when the
  * denominator is 0); stable (>= 0.98f): plane 0, else 1 + first maximum of iou4[p][1..3]; out_iou [P] = iou4 of the chosen plane, out_sel [P]

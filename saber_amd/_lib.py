@@ -134,6 +134,7 @@ SIGNATURES = {
     "saber_k_dec_i2t16": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _vp]),
     "saber_k_dec_t2i": (_i, [_vp, C.c_int64, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_dec_upscale": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "saber_k_hyper_pack": (_i, [_vp, _i, _vp, _vp, _vp]),
     "saber_k_mask_pick": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_mask_select": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "saber_k_iou_live_flags": (_i, [_vp, _i, _f, _vp, _vp, _vp]),

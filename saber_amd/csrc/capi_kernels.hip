@@ -165,7 +165,8 @@ extern "C" int saber_k_dec_t2i(const uint16_t* X, int64_t x_batch_stride, const 
 // ------------------------------------------------------------------------------------------------ head of the mask decoder
 // The ConvTranspose weights arrive in checkpoint layout and go through the packer saber_engine_finalize uses (saber_pack_upscale, engine.hip).
 // They are packed once per call into one device temporary that is released after the launch has completed: the call returns with the
-// stream drained (no scratch kept per thread or per device).
+// stream drained (no scratch kept per thread or per device).  fp32 hyper goes through launch_hyper_pack into the same temporary (the kernel reads
+// the packed hi / lo operand, as in the engine); no counter: `sentinel` counts the stored logits alone.
 extern "C" int saber_k_dec_upscale(const uint16_t* X, const float* w0, const float* b0, const float* ln_gamma, const float* ln_beta, const float* w3, const float* b3,
                                    const float* fs1, const float* fs0, int slot_div, int slot_off, const float* hyper, float* masks4, int P, const uint8_t* live,
                                    const float* iou4, int multimask, unsigned int* sentinel, void* stream) {
@@ -184,7 +185,7 @@ extern "C" int saber_k_dec_upscale(const uint16_t* X, const float* w0, const flo
     if (st != hipSuccess) return kfail(hipGetErrorString(st));
     UpscalePack up;
     saber_pack_upscale(hw0.data(), hb0.data(), hw3.data(), hb3.data(), &up);
-    // one temporary: W1 [256][256] | W2p [128][64] (16-bit operand type) | b1 [256] | b2 [128] (fp32)
+    // one temporary: W1 [256][256] | W2p [128][64] (16-bit operand type) | b1 [256] | b2 [128] (fp32) | hyper_pk [P][256] (16-bit operand type)
     const size_t n1 = up.w1.size(), n2 = up.w2p.size(), w_bytes = (n1 + n2) * sizeof(bf16_t);
     std::vector<unsigned char> host(w_bytes + (up.b1.size() + up.b2.size()) * 4);
     bf16_t* hw = reinterpret_cast<bf16_t*>(host.data());
@@ -196,20 +197,27 @@ extern "C" int saber_k_dec_upscale(const uint16_t* X, const float* w0, const flo
     memcpy(host.data() + w_bytes, up.b1.data(), up.b1.size() * 4);
     memcpy(host.data() + w_bytes + up.b1.size() * 4, up.b2.data(), up.b2.size() * 4);
     unsigned char* dev = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&dev), host.size()) != hipSuccess) return kfail("dec_upscale: allocation of the packed weights failed");
+    if (hipMalloc(reinterpret_cast<void**>(&dev), host.size() + (size_t)P * 256 * sizeof(bf16_t)) != hipSuccess) return kfail("dec_upscale: allocation of the packed weights failed");
     int rc = 0;
     st = hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, s);
     if (st != hipSuccess) rc = kfail(hipGetErrorString(st));
     if (rc == 0) {
         const bf16_t* W1 = reinterpret_cast<const bf16_t*>(dev);
         const float* b1 = reinterpret_cast<const float*>(dev + w_bytes);
-        rc = kcheck(launch_dec_upscale(X, W1, b1, ln_gamma, ln_beta, W1 + n1, b1 + up.b1.size(), fs1, fs0, XMap{0, slot_div, slot_off}, hyper, masks4, P, s, live, iou4,
-                                       multimask, sentinel));
+        bf16_t* hyper_pk = reinterpret_cast<bf16_t*>(dev + host.size());      // (a multiple of 16 bytes; the launchers check the alignment)
+        rc = kcheck(launch_hyper_pack(hyper, P, hyper_pk, nullptr, s));
+        if (rc == 0)
+            rc = kcheck(launch_dec_upscale(X, W1, b1, ln_gamma, ln_beta, W1 + n1, b1 + up.b1.size(), fs1, fs0, XMap{0, slot_div, slot_off}, hyper, hyper_pk, masks4, P, s, live,
+                                           iou4, multimask, sentinel));
     }
     st = hipStreamSynchronize(s);          // the launch has completed (and the upload has left `host`) before either temporary goes
     (void)hipFree(dev);
     if (rc == 0 && st != hipSuccess) rc = kfail(hipGetErrorString(st));
     return rc;
+}
+extern "C" int saber_k_hyper_pack(const float* hyper, int P, uint16_t* out, unsigned int* nonfinite_counter, void* stream) {
+    if (P > 0 && (!hyper || !out)) return kfail("hyper_pack: null pointer");
+    return kcheck(launch_hyper_pack(hyper, P, out, nonfinite_counter, (hipStream_t)stream));
 }
 extern "C" int saber_k_mask_pick(const float* masks4, const float* iou4, int P, int multimask, float* out_iou, int* out_sel, const uint8_t* live, void* stream) {
     if (P > 0 && (!iou4 || !out_iou || (!multimask && !masks4))) return kfail("mask_pick: null pointer");

@@ -1401,11 +1401,52 @@ enum { UPD_NO_GELU = 1, UPD_NO_W1_READ = 2, UPD_NO_W2_READ = 4, UPD_NO_STORE = 8
 #define UP_LDS (UP_W1S + UP_W2S + UP_LNS)
 __device__ __forceinline__ int swz128(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
+// The hypernetwork operand of dec_upscale_kernel, split and packed once per prompt instead of once per (tile, prompt, wave) unit:
+// hyper_pk[p][0 = hi | 1 = lo][mask m][fg][8] in the 16-bit operand type, element j = channel 4 fg + j (j < 4) | 16 + 4 fg + (j - 4) of
+// hyper[p][m][.] (the k-slot order of the hypernetwork MFMA), hi = f2op(v), lo = f2op(v - op2f(hi)).  512 B per prompt, as fp32 hyper.
+// It is also the overflow sentinel's scan of hyper (image_ops.hip nonfinite_scan_kernel: the same grid, the same float4 groups per thread
+// and the same count, one per lane that saw a NaN / inf), so a decode launches as many kernels as before.
+__global__ __launch_bounds__(256) void hyper_pack_kernel(const float* __restrict__ hyper, int64_t n4, bf16_t* __restrict__ out, unsigned int* __restrict__ counter) {
+    unsigned int bad = 0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {      // i = (p * 4 + m) * 8 + c: channels 4 c .. 4 c + 3
+        const f32x4 v = *(reinterpret_cast<const f32x4*>(hyper) + i);
+        const float z = fmaf(v[0], 0.f, fmaf(v[1], 0.f, fmaf(v[2], 0.f, v[3] * 0.f)));
+        bad += (z != z) ? 1u : 0u;
+        float l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) l[j] = v[j] - op2f(f2op(v[j]));
+        const int c = (int)(i & 7);
+        bf16_t* o = out + (i >> 5) * 256 + ((i >> 3) & 3) * 32 + (c & 3) * 8 + (c >> 2) * 4;
+        *reinterpret_cast<uint2*>(o) = make_uint2(pack_op16(v[0], v[1]), pack_op16(v[2], v[3]));
+        *reinterpret_cast<uint2*>(o + 128) = make_uint2(pack_op16(l[0], l[1]), pack_op16(l[2], l[3]));
+    }
+    if (counter) {
+        const unsigned long long m = __ballot(bad != 0);
+        if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(counter, (unsigned int)__popcll(m));
+    }
+}
+
+const char* launch_hyper_pack(const float* hyper, int P, bf16_t* out, unsigned int* counter, hipStream_t s) {
+    if (P <= 0) return nullptr;
+    if (!hyper || !out || ((reinterpret_cast<uintptr_t>(hyper) | reinterpret_cast<uintptr_t>(out)) & 15)) return "hyper_pack: null or unaligned pointer";
+    const int64_t n4 = (int64_t)P * 32;
+    const int64_t blocks = (n4 + 256 * 8 - 1) / (256 * 8);                // launch_nonfinite_scan's grid: the counter counts the same lanes
+    hipLaunchKernelGGL(hyper_pack_kernel, dim3((int)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, hyper, n4, out, counter);
+    return nullptr;
+}
+
+// hyper: hyper_pk of hyper_pack_kernel above (UP_MFMA_HYPER) or the fp32 table [P][4][32] (the VALU product, UP_MFMA_HYPER == 0)
+#if UP_MFMA_HYPER
+typedef bf16_t up_hyper_t;
+#else
+typedef float up_hyper_t;
+#endif
 __global__ __launch_bounds__(UP_THREADS) void dec_upscale_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const float* __restrict__ b1,
                                                                  const float* __restrict__ ln_g, const float* __restrict__ ln_b,
                                                                  const bf16_t* __restrict__ W2p, const float* __restrict__ b2,
                                                                  const float* __restrict__ fs1, const float* __restrict__ fs0, int s_div, int s_off,
-                                                                 const float* __restrict__ hyper, float* __restrict__ masks4, int P,
+                                                                 const up_hyper_t* __restrict__ hyper, float* __restrict__ masks4, int P,
                                                                  const uint8_t* __restrict__ live, const float* __restrict__ iou4, int multimask, int dbg,
                                                                  unsigned long long* __restrict__ stamps, unsigned int* __restrict__ sentinel) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1478,11 +1519,11 @@ __global__ __launch_bounds__(UP_THREADS) void dec_upscale_kernel(const bf16_t* _
         // B-operand fragments of the wave's 16 tokens: lane (fi, fg) holds X[tok][32 ks + 8 fg .. +7], ks = 0..7; one 32-bit lane offset into
         // a per-prompt buffer descriptor (the prompt's 2-MB state)
         const uint32_t xoff = (uint32_t)((tok * DC + 8 * fg) * 2);
-        op16x8 xf[UP_NS][8];
-        auto xload = [&](int p, op16x8 (&dst)[8]) {
+        u32x4 xf[UP_NS][8];              // (bit patterns, cast to the operand type at the MFMA: see the prefetch in the prompt loop)
+        auto xload = [&](int p, u32x4 (&dst)[8]) {
             const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)(X + (int64_t)p * 4096 * DC), 0, 4096 * DC * 2, 0x00020000);
 #pragma unroll
-            for (int ks = 0; ks < 8; ++ks) dst[ks] = __builtin_bit_cast(op16x8, __builtin_amdgcn_raw_buffer_load_b128(xr, xoff + 64 * ks, 0, 0));
+            for (int ks = 0; ks < 8; ++ks) dst[ks] = __builtin_amdgcn_raw_buffer_load_b128(xr, xoff + 64 * ks, 0, 0);
         };
         // output pixels of this lane: token (gy, gx) on the 64x64 grid, ConvT1 position (dy1, dx1); mask k = fg
         int gy, gx;
@@ -1546,17 +1587,13 @@ __global__ __launch_bounds__(UP_THREADS) void dec_upscale_kernel(const bf16_t* _
             // phase B leaves its GELU outputs in, so they are packed into the B operand as they stand.  Every row 4 fg + r of the result is
             // mask fg of token fi: the lane reads its own mask from register 0, no lane movement.  hyper enters as a hi + lo pair of the 16-bit
             // operand type (two MFMAs, exact to 2^-17 / 2^-23); u2 is rounded to that type (2^-9 / 2^-12 per element, averaged over the 32-term sum).
+            // The pair depends on the prompt alone: hyper_pack_kernel has split and packed it, a lane loads its 2 x 16 bytes as they stand.
             op16x8 hy_hi[UP_NS], hy_lo[UP_NS];
 #pragma unroll
             for (int sI = 0; sI < UP_NS; ++sI) {
-                const float* hp = hyper + (int64_t)(cur[sI] < 0 ? cur[0] : cur[sI]) * 128 + (fi >> 2) * 32 + 4 * fg;
-                const float4 a = *reinterpret_cast<const float4*>(hp), b = *reinterpret_cast<const float4*>(hp + 16);
-                const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-                float l[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) l[j] = v[j] - op2f(f2op(v[j]));
-                hy_hi[sI] = pack8_d(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
-                hy_lo[sI] = pack8_d(l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7]);
+                const bf16_t* hp = hyper + (int64_t)(cur[sI] < 0 ? cur[0] : cur[sI]) * 256 + (fi >> 2) * 32 + 8 * fg;
+                hy_hi[sI] = *reinterpret_cast<const op16x8*>(hp);
+                hy_lo[sI] = *reinterpret_cast<const op16x8*>(hp + 128);
             }
 #else
             static_assert(UP_NS == 1, "the VALU hypernetwork product is built for one prompt per iteration");
@@ -1579,16 +1616,19 @@ __global__ __launch_bounds__(UP_THREADS) void dec_upscale_kernel(const bf16_t* _
                     const op16x8 wf = *reinterpret_cast<const op16x8*>(w1s + (UPD(UPD_NO_W1_READ) ? kswz(fi, fg) : kswz(pos * 64 + ni * 16 + fi, ks * 4 + fg)));
 #pragma unroll
                     for (int sI = 0; sI < UP_NS; ++sI) {
-                        if (!UPD(UPD_NO_MFMA_A)) acc[sI][ni] = MFMA_16x16x32(wf, xf[sI][ks], acc[sI][ni], 0, 0, 0);
+                        if (!UPD(UPD_NO_MFMA_A)) acc[sI][ni] = MFMA_16x16x32(wf, __builtin_bit_cast(op16x8, xf[sI][ks]), acc[sI][ni], 0, 0, 0);
                         else acc[sI][ni][0] += __builtin_bit_cast(f32x4, wf)[0] + __builtin_bit_cast(f32x4, xf[sI][ks])[0];
                     }
                 }
             }
             UP_STAMP(0);
-            // the operand registers are free again: the next prompts' rows load while both epilogues and phase B run
+            // the operand registers are free again: the next prompts' rows load while both epilogues and phase B run.  Issued unconditionally
+            // (where no next prompt exists the current one's rows are read again and never used), and xf is carried round the loop as plain
+            // 32-bit words: as 16-bit vectors two of the eight fragments were taken apart and rebuilt at the loop's end (8 v_bfi_b32 vN, 0xffff,
+            // vM, vM per iteration, plain copies); as words but behind the branch the copies go and two registers spill
             if (!UPD(UPD_NO_XLOAD)) {
 #pragma unroll
-                for (int sI = 0; sI < UP_NS; ++sI) if (nxt[sI] >= 0 && nxt[sI] < p_end) xload(nxt[sI], xf[sI]);
+                for (int sI = 0; sI < UP_NS; ++sI) xload(nxt[sI] >= 0 && nxt[sI] < p_end ? nxt[sI] : cur[0], xf[sI]);
             }
             // epilogue A: + (bias + feat_s1), LayerNorm over the 64 channels of (tok, pos), GELU, pack as phase-B operand
             op16x8 uf[UP_NS][2];
@@ -1710,10 +1750,19 @@ __global__ __launch_bounds__(UP_THREADS) void dec_upscale_kernel(const bf16_t* _
 }
 
 const char* launch_dec_upscale(const bf16_t* X, const bf16_t* W1, const float* b1, const float* ln_g, const float* ln_b, const bf16_t* W2p,
-                               const float* b2, const float* fs1, const float* fs0, XMap sm, const float* hyper, float* masks4, int P,
+                               const float* b2, const float* fs1, const float* fs0, XMap sm, const float* hyper_f32, const bf16_t* hyper_pk, float* masks4, int P,
                                hipStream_t s, const uint8_t* live, const float* iou4, int multimask, unsigned int* sentinel) {
     if (P <= 0) return nullptr;
     if (sm.div <= 0) return "dec_upscale: XMap.div must be positive";
+#if UP_MFMA_HYPER
+    const up_hyper_t* hyper = hyper_pk;
+    (void)hyper_f32;
+    if (!hyper || (reinterpret_cast<uintptr_t>(hyper) & 15)) return "dec_upscale: the packed hypernetwork operand is null or unaligned";
+#else
+    const up_hyper_t* hyper = hyper_f32;
+    (void)hyper_pk;
+    if (!hyper) return "dec_upscale: hyper is null";
+#endif
     // one resident workgroup per CU; each takes an equal contiguous share of the UP_TILES x P (tile, prompt) units
     const int n_cu = saber_cu_count();
     const long long units = (long long)UP_TILES * P;

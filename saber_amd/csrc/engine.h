@@ -115,6 +115,7 @@ struct saber_engine {
     bf16_t *fold_q = nullptr, *fold_k = nullptr, *fold_v = nullptr;  // folded operands [P][64][256]
     float *fold_cb = nullptr, *t2i_part = nullptr, *t2i_ml = nullptr;
     float *masks4 = nullptr, *hyper_out = nullptr, *iou4 = nullptr;
+    bf16_t* hyper_pk = nullptr;                                  // [max_prompts][2][4][4][8]: hyper_out as dec_upscale's hi / lo MFMA operand (launch_hyper_pack)
     int* counts_ws = nullptr;
     float* dec_out_masks = nullptr;  // [max_prompts][3][65536] staging when caller passes NULL
     float* dec_out_iou = nullptr;

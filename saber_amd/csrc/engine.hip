@@ -817,6 +817,7 @@ extern "C" int saber_engine_finalize(saber_engine* e) {
     TRY(eng_alloc(e, &e->t2i_ml, P * 8 * 64 * 2));
     TRY(eng_alloc(e, &e->masks4, P * 4 * 65536));
     TRY(eng_alloc(e, &e->hyper_out, P * 128));
+    TRY(eng_alloc(e, &e->hyper_pk, P * 256));
     TRY(eng_alloc(e, &e->iou4, P * 4));
     TRY(eng_alloc(e, &e->counts_ws, 2 * P));
     TRY(eng_alloc(e, &e->dec_out_masks, P * 3 * 65536));
@@ -1410,7 +1411,8 @@ static int decode_chunk(saber_engine* e, int slot0, int per_slot, int p_base, co
     // sentinel: every token-side quantity of the batch ends in the predicted IoUs and the hypernetwork outputs (a NaN / inf row of the image-token
     // state reaches them through the tokens -> image attentions: its score is NaN, so is the softmax sum); the logits are checked where they are stored
     ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_nonfinite_scan(e->iou4, (int64_t)P * 4, e->nonfinite + 1, s));
-    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_nonfinite_scan(e->hyper_out, (int64_t)P * 128, e->nonfinite + 1, s));
+    // (the scan of the hypernetwork outputs rides on the kernel that splits them into dec_upscale's hi / lo operand, once per prompt)
+    ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_hyper_pack(e->hyper_out, P, e->hyper_pk, e->nonfinite + 1, s));
     // IoU pruning (the AMG m2m pass): a single-mask candidate reports iou[0] or max(iou[1..3]) (dynamic multimask selection); when all four are
     // <= the caller's pred_iou_thresh it fails that filter whatever its masks look like, so its 1 MB of planes is neither computed nor read
     const uint8_t* live = nullptr;
@@ -1421,7 +1423,7 @@ static int decode_chunk(saber_engine* e, int slot0, int per_slot, int p_base, co
     // upscaling head fused with the hypernetwork product (dec_upscale_kernel); per prompt, independent of the token count
     ENG_KP(e, PC_DEC_UPSCALE, (double)P * 2.0 * (4096.0 * 256 * 256 + 16384.0 * 64 * 128 + 65536.0 * 32 * 4), (double)P * (4096.0 * 256 * 2 + 4 * 65536.0 * 4),
            launch_dec_upscale(X, e->dc1.w, e->dc1.b, e->up_ln.g, e->up_ln.b, e->dc2p, e->dc2.b, e->fs1 + (size_t)slot0 * 16384 * 64,
-                              e->fs0 + (size_t)slot0 * 65536 * 32, XMap{0, per_slot, p_base}, e->hyper_out, raw4_out ? raw4_out : e->masks4, P, s, live,
+                              e->fs0 + (size_t)slot0 * 65536 * 32, XMap{0, per_slot, p_base}, e->hyper_out, e->hyper_pk, raw4_out ? raw4_out : e->masks4, P, s, live,
                               getenv("SABER_AMD_ALL_PLANES") ? nullptr : e->iou4, multimask, e->nonfinite + 2));      // (development A/B: all four planes)
     return decode_pick_or_select(e, P, multimask, out_lowres, out_iou, raw4_out, out_sel, live, s);
 }

@@ -206,7 +206,7 @@ SABER_OP_FWD(gemm_mlp_rowln_width) SABER_OP_FWD(gemm_mlp_rowln_packed_elems) SAB
 SABER_OP_FWD(launch_layernorm) SABER_OP_FWD(launch_gather_rows) SABER_OP_FWD(launch_add_to_bf16) SABER_OP_FWD(launch_hiera_attention)
 SABER_OP_FWD(launch_prompt_tokens) SABER_OP_FWD(launch_prompt_tokens_multi) SABER_OP_FWD(launch_mask_embed_src) SABER_OP_FWD(launch_mask_hidden) SABER_OP_FWD(launch_embb_tiles)
 SABER_OP_FWD(launch_dec_attention) SABER_OP_FWD(launch_mask_pick) SABER_OP_FWD(launch_iou_live_flags) SABER_OP_FWD(launch_mask_select)
-SABER_OP_FWD(launch_dec_t2i) SABER_OP_FWD(launch_dec_i2t) SABER_OP_FWD(launch_dec_upscale) SABER_OP_FWD(launch_dec_tokens)
+SABER_OP_FWD(launch_dec_t2i) SABER_OP_FWD(launch_dec_i2t) SABER_OP_FWD(launch_dec_upscale) SABER_OP_FWD(launch_hyper_pack) SABER_OP_FWD(launch_dec_tokens)
 SABER_OP_FWD(launch_prompt_tokens16) SABER_OP_FWD(launch_dec_tokens16) SABER_OP_FWD(launch_dec_i2t16)
 SABER_OP_FWD(launch_mask_post) SABER_OP_FWD(launch_gather_masks) SABER_OP_FWD(launch_label_plane) SABER_OP_FWD(launch_pair_intersections) SABER_OP_FWD(launch_unpermute_nchw)
 SABER_OP_FWD(launch_rope) SABER_OP_FWD(launch_softmax_rows) SABER_OP_FWD(launch_conv3x3s2) SABER_OP_FWD(launch_unpack_masks) SABER_OP_FWD(launch_paint_nearest)

@@ -62,8 +62,12 @@ const char* launch_dec_t2i(const bf16_t* X, XMap xm, const bf16_t* pek, const bf
 const char* launch_dec_i2t(const bf16_t* X, XMap xm, const bf16_t* peq, const bf16_t* Kt, const float* tk, float kscale, const float* cb, const bf16_t* Vt,
                            const float* bo, const float* gamma, const float* beta, float eps, bf16_t* Xout, int P, hipStream_t s, const XBuild* build = nullptr);
 const char* launch_dec_upscale(const bf16_t* X, const bf16_t* W1, const float* b1, const float* ln_g, const float* ln_b, const bf16_t* W2p,
-                               const float* b2, const float* fs1, const float* fs0, XMap slot_map, const float* hyper, float* masks4, int P,
+                               const float* b2, const float* fs1, const float* fs0, XMap slot_map, const float* hyper, const bf16_t* hyper_pk, float* masks4, int P,
                                hipStream_t s, const uint8_t* live = nullptr, const float* iou4 = nullptr, int multimask = 0, unsigned int* sentinel = nullptr);
+// hyper_pk [P][2][4][4][8] (16-bit operand type): the hi / lo halves of hyper [P][4][32] in the kernel's k-slot order, written by launch_hyper_pack,
+// which also adds hyper's NaN / inf lanes to *counter (optional) exactly as launch_nonfinite_scan(hyper, 128 P, counter) does.  The kernel reads
+// hyper_pk alone; fp32 hyper is read only by the UP_MFMA_HYPER == 0 build variant (which ignores hyper_pk)
+const char* launch_hyper_pack(const float* hyper, int P, bf16_t* hyper_pk, unsigned int* counter, hipStream_t s);
 // sentinel (optional): += number of lanes that stored a NaN / inf logit (a lane of a workgroup counts once per launch, however many pixels and prompts it
 // stored: non-zero = something overflowed, not a pixel count)
 // live: optional per-prompt flags, prompts with 0 are skipped; iou4 ([P][4], optional): only the planes a multimask / single-mask selection can return are computed
