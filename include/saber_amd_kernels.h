@@ -122,6 +122,13 @@ int saber_k_dwconv7(const float* in, int H, int W, int C, const float* w, const 
 /* the video predictor's mask_downsample: Conv2d(1, 1, k4, s4) */
 /* saber_k_dwconv7 with the weights given as (7,7,C) [tap][channel] */
 int saber_k_dwconv7_t(const float* in, int H, int W, int C, const float* wt, const float* b, float* out, void* stream);
+/* saber_k_conv3x3s2_t / saber_k_dwconv7_t over `batch` objects that share the weights (the tracked objects of a video frame): object i reads
+ * in + i * in_stride and writes out + i * out_stride (strides in elements: multiples of 4, at least one plane when batch > 1; pointers 16-byte
+ * aligned).  Every object's plane is what the single entry writes for it, bit for bit; one weight load serves a block of 4 objects. */
+int saber_k_conv3x3s2_t_batched(const float* in, int64_t in_stride, int H, int W, int Cin, const float* wt, const float* b, int Cout,
+                                float* out, int64_t out_stride, int batch, void* stream);
+int saber_k_dwconv7_t_batched(const float* in, int64_t in_stride, int H, int W, int C, const float* wt, const float* b,
+                              float* out, int64_t out_stride, int batch, void* stream);
 int saber_k_conv4x4s4(const float* in, int H, int W, const float* w, const float* b, float* out, void* stream);
 /* F.interpolate(mode="bilinear", align_corners=False, antialias) of n planes, fused post transform: 0 none, 1 a*sigmoid(v)+c, 2 a*(v>0)+c, 3 a*v+c, 4 (v>=a) */
 int saber_k_resize_plane(const float* in, int n_planes, int H, int W, float* out, int Ho, int Wo, int antialias, int post, float a, float c, void* stream);

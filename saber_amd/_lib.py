@@ -151,6 +151,8 @@ SIGNATURES = {
     "saber_k_unpack_masks": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "saber_k_dwconv7": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_dwconv7_t": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "saber_k_conv3x3s2_t_batched": (_i, [_vp, C.c_int64, _i, _i, _i, _vp, _vp, _i, _vp, C.c_int64, _i, _vp]),
+    "saber_k_dwconv7_t_batched": (_i, [_vp, C.c_int64, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _i, _vp]),
     "saber_k_conv4x4s4": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_resize_plane": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _vp]),
     "saber_k_box_nms": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),

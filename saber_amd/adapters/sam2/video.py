@@ -13,6 +13,8 @@ and backwards).  This module is the Python host of that loop; every arithmetic s
     object pointer   3-layer MLP on the chosen mask token           saber_k_gemm_ld
     memory encoder   mask down-sampler, fuser, projection          saber_k_conv3x3s2, saber_k_layernorm (+GELU), saber_k_dwconv7, saber_k_gemm_ld, saber_k_axpy
     masks            up / down-sampling, "mask for memory"          saber_k_resize_plane, saber_k_conv4x4s4
+With batch_objects on, the memory attention of a frame's objects runs as one batch (_memory_conditioned_batch) and, with batch_tail, so does
+what follows it (_track_tail_batch: saber_k_conv3x3s2_t_batched, saber_k_dwconv7_t_batched, saber_k_gemm_ld_batched, one host wait per frame).
 
 torch is used for device allocation, host<->device copies and a handful of scalar read-backs (argmax of 3 IoU predictions, the sign
 of the object score) - the decisions upstream also takes on the host.  Objects are tracked independently, as upstream does.
@@ -201,13 +203,17 @@ class VideoPredictor:
     """add_new_mask / propagate_in_video of the SAM2 video predictor on one engine handle."""
 
     def __init__(self, engine, weights: Dict[str, np.ndarray], num_maskmem: int = 2, batch_objects: Optional[bool] = None, object_batch: int = 16,
-                 fill_hole_area: int = 0):
+                 fill_hole_area: int = 0, batch_tail: Optional[bool] = None):
         """batch_objects: the memory attention of all objects that are tracked on a frame runs as one set of launches
         (_memory_conditioned_batch; bit-identical to the per-object route); None = the environment switch SABER_AMD_VIDEO_BATCH=1, else off.
         object_batch: most objects per batch (bounds the workspace and activations: ~0.1 GB per object)
         fill_hole_area: upstream's setting of the same name (8 in a default upstream build): every 8-connected component of at most that many
         pixels of the background (logit <= 0) of a frame's 256 x 256 logits is set to the logit 0.1 before the frame's output is stored
-        (_fill_holes).  0 = off: no launch, nothing allocated."""
+        (_fill_holes).  0 = off: no launch, nothing allocated.
+        batch_tail: read only when batch_objects is on: what follows the memory attention on a tracked frame (SAM heads, object pointers,
+        memory encoder, hole fill, the resize of the yield) runs for all of the frame's objects together, with one host wait per frame
+        (_track_tail_batch; bit-identical to the per-object tail).  None = on unless SABER_AMD_VIDEO_BATCH_TAIL=0; False = the per-object tail
+        behind the batched attention."""
         if fill_hole_area < 0:
             raise ValueError("fill_hole_area must be non-negative")
         self.fill_hole_area = int(fill_hole_area)
@@ -217,6 +223,7 @@ class VideoPredictor:
             raise ValueError("object_batch must be at least 1")
         self.batch_objects = os.environ.get("SABER_AMD_VIDEO_BATCH", "0") not in ("", "0") if batch_objects is None else bool(batch_objects)
         self.object_batch = int(object_batch)
+        self.batch_tail = os.environ.get("SABER_AMD_VIDEO_BATCH_TAIL", "1") != "0" if batch_tail is None else bool(batch_tail)
         self.eng, self.lib, self.dev = engine, engine.lib, engine.device
         # 16-bit operand type of the engine handle: every uint16 buffer of this class (GEMM weights, stored memories, attention operands)
         # holds that type's bit patterns
@@ -276,6 +283,8 @@ class VideoPredictor:
         self._flash_ws = None
         self._flash_ws_batch = None
         self._fill_ws = None             # labels + sizes of saber_k_fill_holes
+        self._no_obj_plane = None        # (256,256) of NO_OBJ_SCORE: the logits of an object the heads predict absent (_track_tail_batch)
+        self._pad_point = None           # upstream's padding point (0, 0) with label -1, on the device
         self._mem_pos_all = None         # mem_pos_t as one (num_maskmem, 4096, 64) table for saber_k_membank_assemble
         self.hook = None
         self.images = None
@@ -520,6 +529,43 @@ class VideoPredictor:
         # no_obj_embed_spatial on frames where the object is predicted absent
         bias = self.f32["memory_encoder.out_proj.bias"] if appearing else self.no_obj_spatial_bias
         return self._lin(self._to_bf(p, 4096, 256), "memory_encoder.out_proj", 4096, out_bf=True, bias=bias)
+
+    def _encode_memory_batch(self, raw: torch.Tensor, mfm: torch.Tensor, appearing: int) -> torch.Tensor:
+        """_encode_memory for the B objects of a tracked frame in one set of launches: raw (4096,256) fp32 frame features (shared), mfm
+        (B,1024,1024) fp32 masks for memory, the first `appearing` of them of objects the heads predict present and the rest of absent ones
+        (out_proj adds its bias before the 16-bit rounding, so the two groups are two launches).  Returns (B,4096,64) 16-bit storage, block i =
+        what _encode_memory returns for object i, bit for bit: the convolutions are the batched forms of the same kernels, LayerNorm / axpy /
+        the 16-bit conversion work row by row, and the GEMMs run with the batch dimension of saber_k_gemm_ld_batched."""
+        B = mfm.shape[0]
+        x, H, Cin = mfm, 1024, 1
+        pre = "memory_encoder.mask_downsampler.encoder."
+        for j in range(4):
+            Cout, Ho = Cin * 4, H // 2
+            y = self._new(B, Ho * Ho, Cout)
+            self._ck(self.lib.saber_k_conv3x3s2_t_batched(self._p(x), H * H * Cin, H, H, Cin, self._p(self.conv_t[j]), self._p(self.f32[f"{pre}{3 * j}.bias"]), Cout,
+                                                          self._p(y), Ho * Ho * Cout, B, self._s()))
+            H = Ho
+            x = self._ln(y, f"{pre}{3 * j + 1}", B * H * H, Cout, 1e-6, bf=(j == 3), act=ACT_GELU)
+            Cin = Cout
+        R = 4096 * 256
+        m = self._gemm_b(x, R, pre + "12", B, 4096)                                          # 1x1 conv 256 -> 256
+        p = self._gemm_b(self._to_bf(raw, 4096, 256), 0, "memory_encoder.pix_feat_proj", B, 4096, res=m, stride_res=R)      # the frame's features: shared
+        for i in range(2):
+            f = f"memory_encoder.fuser.layers.{i}."
+            h = self._new(B, 4096, 256)
+            self._ck(self.lib.saber_k_dwconv7_t_batched(self._p(p), R, 64, 64, 256, self._p(self.dw_t[i]), self._p(self.f32[f + "dwconv.bias"]), self._p(h), R, B, self._s()))
+            hn = self._ln(h, f + "norm", B * 4096, 256, 1e-6)
+            h1 = self._gemm_b(hn, R, f + "pwconv1", B, 4096, out_bf=True, act=ACT_GELU)
+            h2 = self._gemm_b(h1, 4096 * 1024, f + "pwconv2", B, 4096)
+            p2 = self._new(B, 4096, 256)
+            self._ck(self.lib.saber_k_axpy(self._p(p), self._p(h2), self._p(self.f32[f + "gamma"]), 1.0, B * 4096, 256, self._p(p2), self._s()))
+            p = p2
+        pb = self._to_bf(p, B * 4096, 256).view(B, 4096, 256)
+        out = self._new(B, 4096, 64, dtype=torch.uint16)
+        for a, b, bias in ((0, appearing, True), (appearing, B, self.no_obj_spatial_bias)):
+            if b > a:
+                self._gemm_b(pb[a:], R, "memory_encoder.out_proj", b - a, 4096, out_bf=True, bias=bias, out=out[a:], stride_out=4096 * 64)
+        return out
 
     # ------------------------------------------------------------------ prompts
     @torch.inference_mode()
@@ -772,12 +818,14 @@ class VideoPredictor:
     # ------------------------------------------------------------------ memory attention of all objects of a frame
     def _gemm_b(self, A, strideA, key, B, M, out_bf=False, res=None, stride_res=0, act=ACT_NONE, bias=True, out=None, stride_out=None):
         """saber_k_gemm_ld for B objects in one launch (the GEMM's batch dimension: every object keeps its own M, so the kernel and the
-        summation order are those of _lin / _gemm on one object).  out (optional): a buffer of B blocks of stride_out elements"""
+        summation order are those of _lin / _gemm on one object).  out (optional): a buffer of B blocks of stride_out elements;
+        bias: True = the layer's own, False = none, a tensor = that one"""
         w = self.bf[key + ".weight"]
         N, K = w.shape
         if out is None:
             out, stride_out = self._new(B, M, N, dtype=torch.uint16 if out_bf else torch.float32), M * N
-        self._ck(self.lib.saber_k_gemm_ld_batched(self._p(A), K, strideA, self._p(w), K, 1 if K % 64 == 0 else 0, self._p(self.f32[key + ".bias"]) if bias else None,
+        bias_t = self.f32[key + ".bias"] if bias is True else None if bias is False else bias
+        self._ck(self.lib.saber_k_gemm_ld_batched(self._p(A), K, strideA, self._p(w), K, 1 if K % 64 == 0 else 0, self._p(bias_t),
                                                   self._p(res), stride_res, None if out_bf else self._p(out), 0 if out_bf else stride_out,
                                                   self._p(out) if out_bf else None, stride_out if out_bf else 0, M, N, K, act, B, self._s()))
         return out
@@ -924,6 +972,68 @@ class VideoPredictor:
         mem = self._encode_memory(raw, mfm, obj_v > 0)
         return {"pred_masks": self._fill_holes(low), "obj_ptr": ptr, "obj": obj_v, "mem": mem}      # filled after the memory encoder, as upstream
 
+    def _track_tail_batch(self, oids: List[int], conds: torch.Tensor, t: int, reverse: bool):
+        """_track_from for all objects tracked on frame t: conds (len(oids),4096,256) = their memory-conditioned features, in the order of
+        oids.  In chunks of at most object_batch objects: the SAM heads of every object are enqueued without a host read between them (the
+        slot's embedding is overwritten in stream order; self._raw[t] is a copy of its own), ONE host wait fetches the chunk's object scores
+        and IoUs, then the object pointers, the memory encoder, the hole fill run once for the chunk.  Returns ([the output of every object, as
+        _track_from returns it, bit for bit], the (len(oids),256,256) stack of their pred_masks when they lie in one tensor in the order of
+        oids, else None)."""
+        raw = self._frame(t, reverse)
+        slot = self._slot(t)
+        if self._pad_point is None:
+            self._pad_point = (torch.zeros(1, 2, device=self.dev), torch.full((1,), -1, dtype=torch.int32, device=self.dev))
+            self._no_obj_plane = torch.full((256, 256), NO_OBJ_SCORE, device=self.dev)
+        pts, lab = self._pad_point
+        eng, results, stack = self.eng, [], None
+        for c0 in range(0, len(oids), self.object_batch):
+            B = min(self.object_batch, len(oids) - c0)
+            # ---- SAM heads, enqueued only: the calls of _sam_heads, their outputs in one buffer per kind.  scores row i = [obj, -, -, -, iou x 3, -]
+            low, scores, toks = self._new(B, 3, 256, 256), self._new(B, 8), self._new(B, 8, 256)
+            for i in range(B):
+                eng._check(self.lib.saber_set_embed_tokens(eng.h, slot, self._p(conds[c0 + i]), self._s()))
+                eng._check(self.lib.saber_decode_points(eng.h, slot, self._p(pts), self._p(lab), 1, 1, None, self._p(low[i]), self._p(scores[i, 4:]),
+                                                        self._p(scores[i]), self._s()))
+                eng._check(self.lib.saber_get_decoder_tokens(eng.h, 1, self._p(toks[i]), self._s()))
+            host = scores.cpu()              # the one synchronisation of the frame's chunk
+            eng.check_finite()               # the engine's overflow counters accumulate until they are read: one check covers every decode above
+            obj_v = [float(host[i, 0]) for i in range(B)]
+            if self.hook is not None:
+                for v in obj_v:
+                    self.hook(v)
+            best = [int(torch.argmax(host[i, 4:7])) for i in range(B)]
+            # ---- the objects the heads predict present come first in the chunk's stacks (out_proj of the memory encoder: two groups)
+            order = [i for i in range(B) if obj_v[i] > 0] + [i for i in range(B) if not obj_v[i] > 0]
+            k = sum(1 for v in obj_v if v > 0)
+            planes = [low[i, best[i]] if obj_v[i] > 0 else self._no_obj_plane for i in order]
+            low_sel = planes[0][None] if B == 1 and k == 1 else torch.stack(planes, 0)         # one present object: its plane where it lies
+            ptrs = None
+            if k:
+                # obj_ptr_proj on the chosen mask tokens: M = 1 per object through the GEMM's batch dimension (an M = k GEMM is another problem)
+                rows = [toks[i, 3 + best[i]:4 + best[i]] for i in order[:k]]
+                tok = rows[0] if k == 1 else torch.cat(rows, 0)
+                h = self._gemm_b(self._to_bf(tok, k, 256), 256, "obj_ptr_proj.layers.0", k, 1, out_bf=True, act=ACT_RELU)
+                h = self._gemm_b(h, 256, "obj_ptr_proj.layers.1", k, 1, out_bf=True, act=ACT_RELU)
+                ptrs = self._gemm_b(h, 256, "obj_ptr_proj.layers.2", k, 1)                     # (k,1,256) fp32
+            mfm = self._new(B, 1024, 1024)
+            self._ck(self.lib.saber_k_resize_plane(self._p(low_sel), B, 256, 256, self._p(mfm), 1024, 1024, 0, 1, 20.0, -10.0, self._s()))
+            mem = self._encode_memory_batch(raw, mfm, k)
+            filled = self._fill_holes(low_sel)                                                  # after the memory encoder, as upstream
+            chunk = [None] * B
+            for j, i in enumerate(order):
+                chunk[i] = {"pred_masks": filled[j], "obj_ptr": ptrs[j] if j < k else self.no_obj_ptr_dev, "obj": obj_v[i], "mem": mem[j]}
+            results += chunk
+            if B == len(oids) and order == list(range(B)):
+                stack = filled
+        return results, stack
+
+    def _resize_planes(self, planes: torch.Tensor, Hv: int, Wv: int) -> torch.Tensor:
+        """_resize of n stacked (256,256) planes to the video size in one launch: (n,Hv,Wv)"""
+        n = planes.shape[0]
+        out = self._new(n, Hv, Wv)
+        self._ck(self.lib.saber_k_resize_plane(self._p(planes), n, 256, 256, self._p(out), Hv, Wv, 0, 0, 0.0, 0.0, self._s()))
+        return out
+
     @torch.inference_mode()
     def propagate_in_video(self, start_frame_idx: int, max_frame_num_to_track: Optional[int] = None, reverse: bool = False) -> Iterator:
         """yields (frame_idx, obj_ids, video_res_mask_logits (n_obj, 1, Hv, Wv) device fp32) like upstream"""
@@ -942,12 +1052,25 @@ class VideoPredictor:
             outs = []
             conds = {}
             if self.batch_objects:
-                # the memory attention of every object tracked on this frame in one set of launches; the SAM heads and the memory encoder
-                # below stay per object (an object's output reads its own memories alone, so the order of the two loops does not matter)
+                # the memory attention of every object tracked on this frame in one set of launches (an object's output reads its own
+                # memories alone, so the order of the two loops does not matter); then the rest of the frame for all of them together
+                # (batch_tail), or per object in the loop below
                 todo = [oid for oid in self.obj_ids if t not in self.out[oid]["cond"]]
                 if todo:
                     raw = self._frame(t, reverse)
-                    conds = dict(zip(todo, self._memory_conditioned_batch(todo, t, raw, reverse)))
+                    rows = self._memory_conditioned_batch(todo, t, raw, reverse)
+                    if self.batch_tail:
+                        tracked, stack = self._track_tail_batch(todo, rows, t, reverse)
+                        for oid, o in zip(todo, tracked):
+                            self.out[oid]["non_cond"][t] = o
+                        for oid in self.obj_ids:
+                            self._tracked[(oid, t)] = reverse
+                        if stack is None or len(todo) != len(self.obj_ids):       # with the planes of the objects this frame is a conditioning frame of
+                            stack = torch.stack([(self.out[oid]["cond"][t] if t in self.out[oid]["cond"] else self.out[oid]["non_cond"][t])["pred_masks"]
+                                                 for oid in self.obj_ids], 0)
+                        yield t, list(self.obj_ids), self._resize_planes(stack, Hv, Wv)[:, None]
+                        continue
+                    conds = dict(zip(todo, rows))
             for oid in self.obj_ids:
                 self._tracked[(oid, t)] = reverse
                 if t in self.out[oid]["cond"]:

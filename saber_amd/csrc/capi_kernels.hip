@@ -298,6 +298,14 @@ extern "C" int saber_k_dwconv7(const float* in, int H, int W, int C, const float
 extern "C" int saber_k_dwconv7_t(const float* in, int H, int W, int C, const float* wt, const float* b, float* out, void* stream) {
     return kcheck(launch_dwconv7_t(in, H, W, C, wt, b, out, (hipStream_t)stream));
 }
+extern "C" int saber_k_conv3x3s2_t_batched(const float* in, int64_t in_stride, int H, int W, int Cin, const float* wt, const float* b, int Cout, float* out,
+                                           int64_t out_stride, int batch, void* stream) {
+    return kcheck(launch_conv3x3s2_t_batched(in, in_stride, H, W, Cin, wt, b, Cout, out, out_stride, batch, (hipStream_t)stream));
+}
+extern "C" int saber_k_dwconv7_t_batched(const float* in, int64_t in_stride, int H, int W, int C, const float* wt, const float* b, float* out, int64_t out_stride,
+                                         int batch, void* stream) {
+    return kcheck(launch_dwconv7_t_batched(in, in_stride, H, W, C, wt, b, out, out_stride, batch, (hipStream_t)stream));
+}
 extern "C" int saber_k_conv4x4s4(const float* in, int H, int W, const float* w, const float* b, float* out, void* stream) {
     return kcheck(launch_conv4x4s4(in, H, W, w, b, out, (hipStream_t)stream));
 }

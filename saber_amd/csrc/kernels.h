@@ -213,6 +213,7 @@ SABER_OP_FWD(launch_rope) SABER_OP_FWD(launch_softmax_rows) SABER_OP_FWD(launch_
 SABER_OP_FWD(launch_conv3x3s2_t) SABER_OP_FWD(launch_dwconv7_t) SABER_OP_FWD(launch_dwconv7) SABER_OP_FWD(launch_conv4x4s4) SABER_OP_FWD(launch_resize_plane)
 SABER_OP_FWD(launch_flash256) SABER_OP_FWD(launch_gauss_mirror) SABER_OP_FWD(launch_axpy) SABER_OP_FWD(launch_bf16_to_f32)
 SABER_OP_FWD(launch_rope_batched) SABER_OP_FWD(launch_flash256_batched) SABER_OP_FWD(launch_membank_assemble)
+SABER_OP_FWD(launch_conv3x3s2_t_batched) SABER_OP_FWD(launch_dwconv7_t_batched)
 #undef SABER_OP_FWD
 #undef SABER_OP_INIT
 #endif

@@ -103,6 +103,12 @@ const char* launch_unpack_masks(const uint32_t* bits, int n, int H, int W, uint8
 const char* launch_paint_nearest(const float* logits, int Hv, int Wv, float thr, int label, uint16_t* plane, int H, int W, int* any_flag, hipStream_t s);
 const char* launch_conv3x3s2_t(const float* in, int H, int W, int Cin, const float* wt, const float* b, int Cout, float* out, hipStream_t s);
 const char* launch_dwconv7_t(const float* in, int H, int W, int C, const float* wt, const float* b, float* out, hipStream_t s);   // weights [49][C]
+// launch_conv3x3s2_t / launch_dwconv7_t over `batch` objects that share the weights: object i reads in + i * in_stride and writes out + i * out_stride
+// (strides in elements, multiples of 4, at least one plane when batch > 1); every object's plane is the single launcher's, bit for bit
+const char* launch_conv3x3s2_t_batched(const float* in, int64_t in_stride, int H, int W, int Cin, const float* wt, const float* b, int Cout, float* out,
+                                       int64_t out_stride, int batch, hipStream_t s);
+const char* launch_dwconv7_t_batched(const float* in, int64_t in_stride, int H, int W, int C, const float* wt, const float* b, float* out, int64_t out_stride,
+                                     int batch, hipStream_t s);
 const char* launch_dwconv7(const float* in, int H, int W, int C, const float* w, const float* b, float* out, hipStream_t s);
 const char* launch_conv4x4s4(const float* in, int H, int W, const float* w, const float* b, float* out, hipStream_t s);
 const char* launch_resize_plane(const float* in, int n_planes, int H, int W, float* out, int Ho, int Wo, int antialias, int post, float a, float c, hipStream_t s);

@@ -328,6 +328,146 @@ const char* launch_conv4x4s4(const float* in, int H, int W, const float* w, cons
     return nullptr;
 }
 
+// ------------------------------------------------------------------------------------------------ the two _t convolutions over a batch of objects
+// The weights are the same for every object of a tracked frame, and conv3x3s2_t_kernel spends one float4 weight load per four FMAs (its
+// input value is a wave-wide broadcast: the kernel lives on L1 traffic).  Here a thread owns one (pixel, 4 channels) for OBJ_BLOCK objects
+// (blockIdx.y = the block of objects): every weight float4 is loaded once and used for all of them.  Object i reads in + i * in_stride and
+// writes out + i * out_stride; its accumulator chain is the single kernel's (bias first, taps in ky, kx, ci order, one fmaf per tap and
+// channel, taps outside the image skipped), so its plane is that kernel's, bit for bit.  Objects beyond the batch in the last block read
+// the batch's last object (in bounds, no divergence) and store nothing.
+constexpr int OBJ_BLOCK = 4;
+#define SABER_FMA4(acc, w4, v)                                                                                             \
+    { acc.x = fmaf(w4.x, v, acc.x); acc.y = fmaf(w4.y, v, acc.y); acc.z = fmaf(w4.z, v, acc.z); acc.w = fmaf(w4.w, v, acc.w); }
+// VEC: Cin is a multiple of 4 and the input values of four taps come in one float4 (the order of the FMAs stays ci ascending)
+template <bool VEC>
+__global__ __launch_bounds__(256) void conv3x3s2_t_batched_kernel(const float* __restrict__ in, int64_t in_stride, int H, int W, int Cin,
+                                                                  const float* __restrict__ wt, const float* __restrict__ b, int Cout,
+                                                                  float* __restrict__ out, int64_t out_stride, int batch) {
+    const int Ho = H >> 1, Wo = W >> 1, c4n = Cout >> 2;
+    const int64_t total = (int64_t)Ho * Wo * c4n;
+    const int o0 = blockIdx.y * OBJ_BLOCK;
+    const float* inb[OBJ_BLOCK];
+#pragma unroll
+    for (int o = 0; o < OBJ_BLOCK; ++o) inb[o] = in + (int64_t)min(o0 + o, batch - 1) * in_stride;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int co = (int)(idx % c4n) * 4;
+        const int64_t pix = idx / c4n;
+        const int ox = (int)(pix % Wo), oy = (int)(pix / Wo);
+        float4 acc[OBJ_BLOCK];
+#pragma unroll
+        for (int o = 0; o < OBJ_BLOCK; ++o) acc[o] = *reinterpret_cast<const float4*>(b + co);
+        for (int ky = 0; ky < 3; ++ky) {
+            const int iy = 2 * oy + ky - 1;
+            if (iy < 0 || iy >= H) continue;
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ix = 2 * ox + kx - 1;
+                if (ix < 0 || ix >= W) continue;
+                const int64_t ioff = ((int64_t)iy * W + ix) * Cin;
+                const float* wp = wt + (int64_t)(ky * 3 + kx) * Cin * Cout + co;
+                if (VEC) {
+                    for (int ci = 0; ci < Cin; ci += 4) {
+                        float4 v[OBJ_BLOCK];
+#pragma unroll
+                        for (int o = 0; o < OBJ_BLOCK; ++o) v[o] = *reinterpret_cast<const float4*>(inb[o] + ioff + ci);
+                        const float4 w0 = *reinterpret_cast<const float4*>(wp + (int64_t)ci * Cout);
+                        const float4 w1 = *reinterpret_cast<const float4*>(wp + (int64_t)(ci + 1) * Cout);
+                        const float4 w2 = *reinterpret_cast<const float4*>(wp + (int64_t)(ci + 2) * Cout);
+                        const float4 w3 = *reinterpret_cast<const float4*>(wp + (int64_t)(ci + 3) * Cout);
+#pragma unroll
+                        for (int o = 0; o < OBJ_BLOCK; ++o) {
+                            SABER_FMA4(acc[o], w0, v[o].x) SABER_FMA4(acc[o], w1, v[o].y) SABER_FMA4(acc[o], w2, v[o].z) SABER_FMA4(acc[o], w3, v[o].w)
+                        }
+                    }
+                } else {
+                    for (int ci = 0; ci < Cin; ++ci) {
+                        const float4 w4 = *reinterpret_cast<const float4*>(wp + (int64_t)ci * Cout);
+#pragma unroll
+                        for (int o = 0; o < OBJ_BLOCK; ++o) {
+                            const float v = inb[o][ioff + ci];
+                            SABER_FMA4(acc[o], w4, v)
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < OBJ_BLOCK; ++o)
+            if (o0 + o < batch) *reinterpret_cast<float4*>(out + (int64_t)(o0 + o) * out_stride + pix * Cout + co) = acc[o];
+    }
+}
+__global__ __launch_bounds__(256) void dwconv7_t_batched_kernel(const float* __restrict__ in, int64_t in_stride, int H, int W, int C,
+                                                                const float* __restrict__ wt, const float* __restrict__ b, float* __restrict__ out,
+                                                                int64_t out_stride, int batch) {
+    const int c4n = C >> 2;
+    const int64_t total = (int64_t)H * W * c4n;
+    const int o0 = blockIdx.y * OBJ_BLOCK;
+    const float* inb[OBJ_BLOCK];
+#pragma unroll
+    for (int o = 0; o < OBJ_BLOCK; ++o) inb[o] = in + (int64_t)min(o0 + o, batch - 1) * in_stride;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int c = (int)(idx % c4n) * 4;
+        const int64_t pix = idx / c4n;
+        const int x = (int)(pix % W), y = (int)(pix / W);
+        float4 acc[OBJ_BLOCK];
+#pragma unroll
+        for (int o = 0; o < OBJ_BLOCK; ++o) acc[o] = *reinterpret_cast<const float4*>(b + c);
+#pragma unroll
+        for (int ky = 0; ky < 7; ++ky) {
+            const int iy = y + ky - 3;
+            if (iy < 0 || iy >= H) continue;
+#pragma unroll
+            for (int kx = 0; kx < 7; ++kx) {
+                const int ix = x + kx - 3;
+                if (ix < 0 || ix >= W) continue;
+                const int64_t ioff = ((int64_t)iy * W + ix) * C + c;
+                const float4 w4 = *reinterpret_cast<const float4*>(wt + (int64_t)(ky * 7 + kx) * C + c);
+#pragma unroll
+                for (int o = 0; o < OBJ_BLOCK; ++o) {
+                    const float4 v = *reinterpret_cast<const float4*>(inb[o] + ioff);
+                    acc[o].x = fmaf(w4.x, v.x, acc[o].x); acc[o].y = fmaf(w4.y, v.y, acc[o].y);
+                    acc[o].z = fmaf(w4.z, v.z, acc[o].z); acc[o].w = fmaf(w4.w, v.w, acc[o].w);
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < OBJ_BLOCK; ++o)
+            if (o0 + o < batch) *reinterpret_cast<float4*>(out + (int64_t)(o0 + o) * out_stride + pix * C + c) = acc[o];
+    }
+}
+#undef SABER_FMA4
+static const char* batched_conv_args(const void* in, int64_t in_stride, int64_t in_plane, const void* wt, const void* b, const void* out, int64_t out_stride,
+                                     int64_t out_plane, int batch) {
+    if (batch < 1 || batch > 65535 * OBJ_BLOCK) return "batched convolution: batch must be in 1..262140";
+    if (!in || !wt || !b || !out) return "batched convolution: null pointer";
+    if (in_plane <= 0 || out_plane <= 0) return "batched convolution: empty plane";
+    if (in_stride < 0 || out_stride < 0 || (batch > 1 && (in_stride < in_plane || out_stride < out_plane)))
+        return "batched convolution: an object stride is smaller than one plane";
+    if ((in_stride | out_stride) & 3) return "batched convolution: object strides must be multiples of 4 elements";
+    if (((uintptr_t)in | (uintptr_t)wt | (uintptr_t)b | (uintptr_t)out) & 15) return "batched convolution: pointers must be 16-byte aligned";
+    return nullptr;
+}
+const char* launch_conv3x3s2_t_batched(const float* in, int64_t in_stride, int H, int W, int Cin, const float* wt, const float* b, int Cout, float* out,
+                                       int64_t out_stride, int batch, hipStream_t s) {
+    if (H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return "conv3x3s2_t_batched: empty problem";
+    if ((H | W) & 1) return "conv3x3s2_t_batched: H and W must be even";
+    if (Cout & 3) return "conv3x3s2_t_batched: Cout must be a multiple of 4";
+    if (const char* m = batched_conv_args(in, in_stride, (int64_t)H * W * Cin, wt, b, out, out_stride, (int64_t)(H / 2) * (W / 2) * Cout, batch)) return m;
+    const int64_t total = (int64_t)(H / 2) * (W / 2) * (Cout / 4);
+    const dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 65536), (batch + OBJ_BLOCK - 1) / OBJ_BLOCK);
+    if (Cin & 3) hipLaunchKernelGGL(conv3x3s2_t_batched_kernel<false>, grid, dim3(256), 0, s, in, in_stride, H, W, Cin, wt, b, Cout, out, out_stride, batch);
+    else hipLaunchKernelGGL(conv3x3s2_t_batched_kernel<true>, grid, dim3(256), 0, s, in, in_stride, H, W, Cin, wt, b, Cout, out, out_stride, batch);
+    return nullptr;
+}
+const char* launch_dwconv7_t_batched(const float* in, int64_t in_stride, int H, int W, int C, const float* wt, const float* b, float* out, int64_t out_stride,
+                                     int batch, hipStream_t s) {
+    if (H <= 0 || W <= 0 || C <= 0) return "dwconv7_t_batched: empty problem";
+    if (C & 3) return "dwconv7_t_batched: C must be a multiple of 4";
+    if (const char* m = batched_conv_args(in, in_stride, (int64_t)H * W * C, wt, b, out, out_stride, (int64_t)H * W * C, batch)) return m;
+    hipLaunchKernelGGL(dwconv7_t_batched_kernel, dim3(grid_for((int64_t)H * W * (C / 4)), (batch + OBJ_BLOCK - 1) / OBJ_BLOCK), dim3(256), 0, s, in, in_stride, H, W, C,
+                       wt, b, out, out_stride, batch);
+    return nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------ plane resize
 // ATen's separable rule (same index / weight arithmetic as resize_normalize_kernel in image_ops.hip): antialias = 0 is
 // F.interpolate(mode="bilinear", align_corners=False), antialias = 1 adds the triangle filter of the down-sampling ratio.
