@@ -134,7 +134,11 @@ int saber_get_decoder_tokens(saber_engine* e, int n, float* out_dev, void* strea
  * shard over ranks; the tracking chain that consumes them is sequential.  Upstream keeps these per-frame features in
  * inference_state["cached_features"], sam2_video_predictor.py).  n consecutive slots from slot0, each as three fp32 device arrays in the
  * engine's token order: image_embed 4096 x 256, feat_s1 16384 x 64, feat_s0 65536 x 32.  import marks the slots as encoded; only
- * meaningful between handles built from the same model configuration and weights. */
+ * meaningful between handles built from the same model configuration and weights.  Both are plain device copies on `stream`, so a slot that
+ * was exported and imported again decodes bit-identically.  The video predictor's frame-feature store (VideoPredictor(frame_store_gb=...))
+ * is that cache on one handle: a window's newly encoded slots are exported to rows of three (rows, size) fp32 arrays - before
+ * saber_set_embed_tokens replaces their image_embed - and a later window imports the frames it finds there instead of encoding them;
+ * n consecutive slots take n consecutive rows, so the row pointers are passed with their offset. */
 int saber_export_slots(saber_engine* e, int slot0, int n, float* emb_dev, float* fs1_dev, float* fs0_dev, void* stream);
 int saber_import_slots(saber_engine* e, int slot0, int n, const float* emb_dev, const float* fs1_dev, const float* fs0_dev, void* stream);
 

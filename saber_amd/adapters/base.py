@@ -23,6 +23,9 @@ class SAM2AdapterConfig(BaseModel):
     # video path: background components of at most this many pixels of the tracked 256 x 256 mask logits are filled (upstream SAM2's
     # fill_hole_area; a default upstream build with its CUDA extension uses 8).  None -> SABER_AMD_FILL_HOLE_AREA, else 0 (off)
     fill_hole_area: Optional[int] = None
+    # video path: GiB of device memory for the frame-feature store (16 MiB per frame: a frame of a volume goes through the encoder once,
+    # whatever the number of seeds, directions and slabs).  None -> SABER_AMD_VIDEO_STORE_GB, else 0 (off)
+    frame_store_gb: Optional[float] = None
     light_modality: bool = False
     amg_cfg: Optional[Any] = None      # cfgAMG instance; None -> cfgAMG() defaults
     min_mask_area: int = 50
@@ -42,6 +45,13 @@ class SAM2AdapterConfig(BaseModel):
     def _check_cfg(cls, v):
         if v not in _TRUNKS:
             raise ValueError(f"cfg must be one of tiny/small/base/large, got '{v}'")
+        return v
+
+    @field_validator("frame_store_gb")
+    @classmethod
+    def _check_frame_store_gb(cls, v):
+        if v is not None and not v >= 0:
+            raise ValueError("frame_store_gb must be non-negative")
         return v
 
 

@@ -66,7 +66,8 @@ class SAM2Adapter(BaseAdapter):
             # box or several clicks runs on the handle's 16-bit decoder kernels (16-token route)
             eng = get_engine(self._config.cfg, self.device, self._config.checkpoint, max_images=16, max_prompts=8, replica=1000, multipoint=True)
             W = pretrained_weights.load_weights(self._config.cfg, self._config.checkpoint, video=True)
-            self._video_predictor = VideoPredictor(eng, W, num_maskmem=self._config.num_maskmem, fill_hole_area=self._fill_hole_area())
+            self._video_predictor = VideoPredictor(eng, W, num_maskmem=self._config.num_maskmem, fill_hole_area=self._fill_hole_area(),
+                                                   frame_store_gb=self._config.frame_store_gb)
         return self._video_predictor
 
     def _fill_hole_area(self) -> int:

@@ -134,6 +134,36 @@ def group_by_signature(oids: List[int], signatures: List[tuple], object_batch: i
     return [g[i:i + object_batch] for g in groups.values() for i in range(0, len(g), object_batch)]
 
 
+# One frame in the frame-feature store: what saber_export_slots writes for one slot (image_embed 4096 x 256, feat_s1 16384 x 64, feat_s0
+# 65536 x 32), fp32 whatever the handle's operand type: 16 MiB
+FRAME_STORE_SIZES = (4096 * 256, 16384 * 64, 65536 * 32)
+FRAME_STORE_BYTES = 4 * sum(FRAME_STORE_SIZES)
+
+
+def frame_store_budget(frame_store_gb: Optional[float] = None) -> int:
+    """Bytes the frame-feature store may take: frame_store_gb GiB; None = the environment's SABER_AMD_VIDEO_STORE_GB, else 0 (off)."""
+    if frame_store_gb is None:
+        frame_store_gb = float(os.environ.get("SABER_AMD_VIDEO_STORE_GB") or 0)
+    frame_store_gb = float(frame_store_gb)
+    if not frame_store_gb >= 0:
+        raise ValueError("frame_store_gb must be non-negative")
+    return int(frame_store_gb * 2 ** 30)
+
+
+def frame_store_rows(budget_bytes: int, num_frames: int) -> int:
+    """Frames the store holds: as many whole frames as the budget pays for, at most the volume's own"""
+    return max(0, min(int(budget_bytes) // FRAME_STORE_BYTES, int(num_frames)))
+
+
+def plan_window(t0: int, t1: int, stored, free_rows: int) -> Tuple[List[int], List[int], bool]:
+    """How the frame-feature store serves the window [t0, t1): (the window's frames that are not in `stored`, ascending; those of them that
+    get one of the `free_rows` rows; whether the window is served from the store).  Rows are allotted first come and never given back, so a
+    window is served only when every missing frame gets a row; otherwise it is encoded as a whole, as without the store, and stores nothing."""
+    missing = [t for t in range(t0, t1) if t not in stored]
+    served = len(missing) <= free_rows
+    return missing, (missing if served else []), served
+
+
 def load_tomogram_frames(tomogram: np.ndarray, image_size: int = 1024, light_modality: bool = False) -> np.ndarray:
     """TomogramPreprocessor as the adapter applies it (saber/adapters/preprocessing.py:27-76 via predictor.py:98-105): min-max to [-1,1],
     per-slice resize to image_size (skimage.transform.resize(anti_aliasing=True): the identity at image_size, order-1 interpolation at
@@ -203,7 +233,7 @@ class VideoPredictor:
     """add_new_mask / propagate_in_video of the SAM2 video predictor on one engine handle."""
 
     def __init__(self, engine, weights: Dict[str, np.ndarray], num_maskmem: int = 2, batch_objects: Optional[bool] = None, object_batch: int = 16,
-                 fill_hole_area: int = 0, batch_tail: Optional[bool] = None):
+                 fill_hole_area: int = 0, batch_tail: Optional[bool] = None, frame_store_gb: Optional[float] = None):
         """batch_objects: the memory attention of all objects that are tracked on a frame runs as one set of launches
         (_memory_conditioned_batch; bit-identical to the per-object route); None = the environment switch SABER_AMD_VIDEO_BATCH=1, else off.
         object_batch: most objects per batch (bounds the workspace and activations: ~0.1 GB per object)
@@ -213,10 +243,24 @@ class VideoPredictor:
         batch_tail: read only when batch_objects is on: what follows the memory attention on a tracked frame (SAM heads, object pointers,
         memory encoder, hole fill, the resize of the yield) runs for all of the frame's objects together, with one host wait per frame
         (_track_tail_batch; bit-identical to the per-object tail).  None = on unless SABER_AMD_VIDEO_BATCH_TAIL=0; False = the per-object tail
-        behind the batched attention."""
+        behind the batched attention.
+        frame_store_gb: GiB of device memory for the frame-feature store: the encoder outputs of a frame (16 MiB of fp32, what
+        saber_export_slots writes for a slot) are kept when a window is encoded and copied back (saber_import_slots) when a later window
+        needs the frame again - another seed, the other direction, another slab of the same volume - so that a frame goes through the
+        encoder once per volume.  Rows = budget // 16 MiB, at most the volume's frames, allocated on first use and allotted first come
+        (no eviction): a window with a frame that is neither stored nor can get a row is encoded as a whole, as without the store.  The
+        store outlives reset_state(), and init_state() with frames bit-equal to the loaded ones; drop_frame_store() frees it.  Same bits as
+        without it.  Bypassed while window encodes shard over ranks (_ranks()[0] > 1).  None = the environment's SABER_AMD_VIDEO_STORE_GB,
+        else 0 = off: no launch, nothing allocated."""
         if fill_hole_area < 0:
             raise ValueError("fill_hole_area must be non-negative")
         self.fill_hole_area = int(fill_hole_area)
+        self.frame_store_budget = frame_store_budget(frame_store_gb)
+        self.encoded_frames = 0          # frames sent through eng.encode since construction (every route)
+        self.restored_frames = 0         # frames copied from the store into a slot
+        self._store = None               # the three (rows, size) fp32 tensors of FRAME_STORE_SIZES
+        self._store_row: Dict[int, int] = {}     # frame -> its row
+        self._frames_dev = None
         if num_maskmem > 7:
             raise ValueError("num_maskmem must be at most 7")
         if object_batch < 1:
@@ -338,13 +382,80 @@ class VideoPredictor:
         self.temp: Dict[int, dict] = {}
         self._raw: Dict[int, torch.Tensor] = {}
         self._win = (0, 0)
-        self._frames_dev = None
+        if self.frame_store_budget >= FRAME_STORE_BYTES:
+            # the store belongs to the frames it was computed from: the stack is uploaded now (a copy of this predictor's own: what the caller
+            # does to a device tensor afterwards cannot reach it) and the store survives only if the stack it came from has the same bits
+            held, new = self._frames_dev, self._upload_frames()
+            if isinstance(frames, torch.Tensor) and new.data_ptr() == frames.data_ptr():
+                new = new.clone()
+            if held is not None and held.shape == new.shape and torch.equal(held, new):
+                new = held
+            else:
+                self.drop_frame_store()
+            self._frames_dev = new
+        else:
+            self._frames_dev = None
         self._points = {}                # (obj_id, frame_idx) -> (points in model pixels (k,2), labels (k,)): the clicks a frame has accumulated
         self._tracked = {}               # (obj_id, frame_idx) -> reverse flag of the propagation that last went over the frame (upstream: frames_tracked_per_obj)
 
     def reset_state(self):
+        """prompts and tracking results go; the loaded frames and the frame-feature store stay"""
         self.obj_ids, self.out, self.temp, self._raw, self._win = [], {}, {}, {}, (0, 0)
         self._points, self._tracked = {}, {}
+
+    def _upload_frames(self) -> torch.Tensor:
+        return (self.images.to(self.dev, dtype=torch.float32).contiguous() if isinstance(self.images, torch.Tensor) else
+                torch.from_numpy(np.ascontiguousarray(self.images, dtype=np.float32)).to(self.dev))
+
+    # ------------------------------------------------------------------ frame-feature store
+    @property
+    def stored_frames(self) -> int:
+        """rows of the frame-feature store in use"""
+        return len(self._store_row)
+
+    @property
+    def store_bytes(self) -> int:
+        """device memory the frame-feature store holds now"""
+        return 0 if self._store is None else self._store[0].shape[0] * FRAME_STORE_BYTES
+
+    def drop_frame_store(self):
+        """frees the frame-feature store; the next window allocates it again"""
+        self._store, self._store_row = None, {}
+
+    def _store_ptrs(self, row: int):
+        return [C.c_void_p(s.data_ptr() + row * s.shape[1] * 4) for s in self._store]
+
+    def _window_from_store(self, t0: int, t1: int, missing: List[int]):
+        """The window [t0, t1) into slots 0..t1-t0-1 through the store (plan_window said it can be served): the missing frames go through the
+        encoder as one batched pass into slots 0.., are exported to their rows at once - _sam_heads overwrites a slot's image_embed with the
+        memory-conditioned tokens - and every frame that is not yet in its slot is imported.  Bit-identical to encoding the window, because
+        the encoder's per-image results do not depend on the batch they ran in (tests/test_gpu_graphs.py) and export / import are copies."""
+        rows = frame_store_rows(self.frame_store_budget, self.num_frames)
+        if self._store is None:
+            self._store = [torch.empty((rows, sz), dtype=torch.float32, device=self.dev) for sz in FRAME_STORE_SIZES]
+        m = len(missing)
+        if m:
+            # crop boxes over the (frames * 1024, 1024) view of the stack from the first to the last missing frame: they need not be contiguous
+            a, b = missing[0], missing[-1] + 1
+            self.eng.encode(self._frames_dev[a:b].view((b - a) * 1024, 1024), crop_boxes=[[0, (f - a) * 1024, 1024, (f - a + 1) * 1024] for f in missing],
+                            slot0=0, normalised_grey=True)
+            self.encoded_frames += m
+            r0 = len(self._store_row)
+            assert r0 + m <= rows
+            self.eng._check(self.lib.saber_export_slots(self.eng.h, 0, m, *self._store_ptrs(r0), self._s()))
+            for i, f in enumerate(missing):
+                self._store_row[f] = r0 + i
+        # frame t0 + j belongs in slot j; missing[j] is there already when it is the window's j-th frame.  Runs of consecutive rows are one call
+        k = t1 - t0
+        todo = [j for j in range(k) if not (j < m and missing[j] == t0 + j)]
+        i = 0
+        while i < len(todo):
+            j, r, n = todo[i], self._store_row[t0 + todo[i]], 1
+            while i + n < len(todo) and todo[i + n] == j + n and self._store_row[t0 + j + n] == r + n:
+                n += 1
+            self.eng._check(self.lib.saber_import_slots(self.eng.h, j, n, *self._store_ptrs(r), self._s()))
+            i += n
+        self.restored_frames += len(todo)
 
     def _frame(self, t: int, reverse: bool = False) -> torch.Tensor:
         """RAW top-level features of frame t (without no_mem_embed) as (4096,256) fp32 row-major tokens.  Frames are encoded a WINDOW at a
@@ -356,15 +467,22 @@ class VideoPredictor:
         B = self.eng.max_images
         t0, t1 = (max(0, t - B + 1), t + 1) if reverse else (t, min(self.num_frames, t + B))
         if self._frames_dev is None:
-            self._frames_dev = (self.images.to(self.dev, dtype=torch.float32).contiguous() if isinstance(self.images, torch.Tensor) else
-                                torch.from_numpy(np.ascontiguousarray(self.images, dtype=np.float32)).to(self.dev))
+            self._frames_dev = self._upload_frames()
         k = t1 - t0
         world, rank = self._ranks()
+        # the frame-feature store is consulted here alone, where a window would be encoded; sharded window encodes bypass it
+        rows = frame_store_rows(self.frame_store_budget, self.num_frames) if world == 1 else 0
+        missing, _, served = plan_window(t0, t1, self._store_row, rows - len(self._store_row)) if rows else ([], [], False)
         if world > 1:
             self._encode_window_sharded(t0, t1, world, rank)
+            a, b = window_shares(k, world)[rank]
+            self.encoded_frames += b - a
+        elif served:
+            self._window_from_store(t0, t1, missing)
         else:
             self.eng.encode(self._frames_dev[t0:t1].view(k * 1024, 1024), crop_boxes=[[0, i * 1024, 1024, (i + 1) * 1024] for i in range(k)],
                             slot0=0, normalised_grey=True)
+            self.encoded_frames += k
         self._raw, self._win = {}, (t0, t1)
         for i in range(k):
             emb = self._new(4096, 256)

@@ -27,18 +27,27 @@ class tomoSegmenter(saber3D):
     def __init__(self, deviceID: int = 0, cfg: Optional[AdapterConfig] = None, amg_cfg: Optional[cfgAMG] = None, min_mask_area: int = 50):
         super().__init__(deviceID=deviceID, cfg=cfg, amg_cfg=amg_cfg, min_mask_area=min_mask_area)
         self.filter_threshold = 0.5
+        self._prepared = None               # (the volume, prepare_volume of it) while one call segments several slabs of it
+
+    @torch.inference_mode()
+    def prepare_volume(self, vol):
+        """The part of segment_slab that does not depend on the slab: z-Gaussian (sigma 5) and normalisation of the whole volume, on the
+        host for a numpy volume, on the device for a CUDA tensor.  `vol` itself is only read."""
+        if isinstance(vol, torch.Tensor):
+            if not volprep.is_device_volume(vol) or vol.dim() != 3:
+                raise TypeError("segment_slab: a tensor volume must be a (Z,H,W) CUDA tensor of float32, int16, uint16 or uint8")
+            # the smoothed copy is this segmenter's own, so it is normalised in place
+            smoothed, minmax = volprep.correlate1d_zero(vol, make_gaussian_kernel(5), dim=0, minmax=True)
+            return preprocess.normalize_(smoothed, minmax)
+        return preprocess.normalize(gaussian_smoothing_z(vol, 5, dim=0))
 
     @torch.inference_mode()
     def segment_slab(self, vol, slab_thickness: int = 10, zSlice: Optional[int] = None, display: bool = True,
                      text: Optional[str] = None, target_class: Optional[int] = 1):
-        if isinstance(vol, torch.Tensor):
-            if not volprep.is_device_volume(vol) or vol.dim() != 3:
-                raise TypeError("segment_slab: a tensor volume must be a (Z,H,W) CUDA tensor of float32, int16, uint16 or uint8")
-            # the smoothed copy is this segmenter's own, so it is normalised in place; `vol` itself is only read
-            smoothed, minmax = volprep.correlate1d_zero(vol, make_gaussian_kernel(5), dim=0, minmax=True)
-            self.vol = preprocess.normalize_(smoothed, minmax)
+        if self._prepared is not None and self._prepared[0] is vol:
+            self.vol = self._prepared[1]
         else:
-            self.vol = preprocess.normalize(gaussian_smoothing_z(vol, 5, dim=0))
+            self.vol = self.prepare_volume(vol)
         if zSlice is None:
             zSlice = int(self.vol.shape[0] // 2)
         self.image0 = preprocess.project_tomogram(self.vol, zSlice, slab_thickness)
@@ -105,16 +114,22 @@ class multiDepthTomoSegmenter(tomoSegmenter):
             combined = torch.zeros(tuple(vol.shape), dtype=torch.int16, device=labelvol.require_device(self.device, "multiDepthTomoSegmenter with device_volumes"))
         else:
             combined = np.zeros(vol.shape, dtype=np.uint16)
-        for i in range(num_slabs):
-            centre = int(depth // 2 + (i - num_slabs // 2) * delta_z)
-            if centre < 0 or centre >= depth:
-                print(f"Skipping slab {i}: slab_center={centre} out of range (0-{depth - 1})")
-                continue
-            masks3d = self.segment_vol(vol, thickness, zSlice=centre, display=False)
-            if masks3d is None:
-                continue
-            if self.device_volumes:
-                labelvol.merge_max_u16_(combined, masks3d, binarize=True)
-            else:
-                np.maximum(combined, (masks3d > 0).astype(np.uint16), out=combined)
+        # the volume is prepared once for all slabs: every slab's set_volume then loads bit-equal frames, which is what lets the video
+        # predictor keep its frame-feature store (SAM2AdapterConfig.frame_store_gb) from one slab to the next
+        self._prepared = (vol, self.prepare_volume(vol))
+        try:
+            for i in range(num_slabs):
+                centre = int(depth // 2 + (i - num_slabs // 2) * delta_z)
+                if centre < 0 or centre >= depth:
+                    print(f"Skipping slab {i}: slab_center={centre} out of range (0-{depth - 1})")
+                    continue
+                masks3d = self.segment_vol(vol, thickness, zSlice=centre, display=False)
+                if masks3d is None:
+                    continue
+                if self.device_volumes:
+                    labelvol.merge_max_u16_(combined, masks3d, binarize=True)
+                else:
+                    np.maximum(combined, (masks3d > 0).astype(np.uint16), out=combined)
+        finally:
+            self._prepared = None
         return self._stitch_device(combined) if self.device_volumes else utils.separate_masks(combined)
