@@ -165,6 +165,25 @@ int saber_decode_prompts(saber_engine* e, int slot, const float* pts_dev, const 
 int saber_amg_generate(saber_engine* e, const float* img_dev, int H, int W, int channels, const saber_amg_params* params,
                        uint32_t* out_bits_dev, int max_masks, saber_mask_meta* out_meta_host, int* out_count, void* stream);
 
+/* SAM2AutomaticMaskGenerator.postprocess_small_regions (upstream's min_mask_region_area > 0; there a host loop over OpenCV calls) on the final
+ * masks of one image, on the device.  bits_in_dev: the (n,H,W32) rows saber_amg_generate returned, meta_host: their n records (in / out).
+ *   1. every mask loses its 8-connected background components (holes) with fewer than min_area pixels, then - on that result - its
+ *      8-connected foreground components (islands) with fewer than min_area pixels; if all islands are below min_area the largest stays
+ *      (saber_k_mask_small_regions in include/saber_amd_kernels.h has the details and the one deviation from OpenCV's tie-break);
+ *   2. a mask in which either pass met such a component is "changed" and scores 0, an untouched one 1; boxes are the tight boxes of the
+ *      new masks ([x0, y0, x1, y1] with inclusive maxima as floats, [0, 0, 0, 0] when empty);
+ *   3. greedy box NMS as torchvision.ops.nms: stable descending score order, fp32 IoU with area = (x2 - x1) (y2 - y1), suppressed when
+ *      IoU > nms_thresh (upstream passes max(box_nms_thresh, crop_nms_thresh));
+ *   4. the survivors in NMS order (untouched masks in their order, then changed masks in theirs) -> bits_out_dev rows 0 .. *out_count - 1
+ *      and meta_host[0 .. *out_count): a surviving untouched mask keeps its record byte for byte, a changed one gets area = its new pixel
+ *      count and bbox_xywh = [x0, y0, x1 - x0, y1 - y0]; predicted_iou, stability_score, point_xy and crop_box_xywh are never modified.
+ * bits_out_dev: room for n rows, must not overlap bits_in_dev (which is left as it is).  Only a created handle is needed (no weights).
+ * The label workspace on the handle is bounded (at most 128 MiB, at least one mask: the masks are run in chunks); the cleaned rows of the
+ * call are staged in packed form.  n <= 12288 (the device NMS), H * W < 2^31, min_area >= 1; n = 0 succeeds with *out_count = 0.
+ * One host synchronisation, which returns the count, the keep list and the per-mask results. */
+int saber_amg_postprocess_small_regions(saber_engine* e, const uint32_t* bits_in_dev, int n, int H, int W, saber_mask_meta* meta_host, int min_area,
+                                        float nms_thresh, uint32_t* bits_out_dev, int* out_count, void* stream);
+
 /* Weight format of the Hiera stage-2 / stage-3 block GEMMs (qkv, proj, fc1, fc2: 94 % of the encoder's weights), to be chosen before
  * saber_engine_finalize.  SABER_WEIGHTS_FP8_E4M3 (BASELINE configs[4], "fp8 weights"): every output row is quantised to OCP e4m3fn with
  * one power-of-two scale per row (round to nearest even, saturating at 448).  The MFMA operands stay bf16 (activations are bf16, and the

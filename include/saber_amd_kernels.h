@@ -117,6 +117,24 @@ int saber_k_unpack_masks(const uint32_t* bits, int n, int H, int W, uint8_t* out
  * is written.  Five launches on `stream`; no synchronisation and no allocation inside. */
 int saber_k_fill_holes(const float* in, int n_planes, int H, int W, int max_area, float fill_value, float* out, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* Small-region clean-up of bit-packed masks (csrc/smallregions.hip): upstream's remove_small_regions in both modes, as
+ * SAM2AutomaticMaskGenerator.postprocess_small_regions applies it when min_mask_region_area > 0.  bits_in / bits_out: (n,H,W32) uint32 rows,
+ * W32 = ceil(W / 32), bit b of word w of a row = pixel 32w+b; bits at x >= W are not pixels: they are ignored on input and zero on output.
+ * Each mask on its own, over the whole H x W plane, rows never wrap and masks never touch:
+ *   1. holes: every 8-connected component of the background with FEWER than min_area pixels becomes foreground (also at the image border);
+ *   2. islands, on the result of 1: every 8-connected foreground component with fewer than min_area pixels is removed; when all of them
+ *      are below min_area the largest stays, on a tie the one whose first pixel comes first in raster order (scipy.ndimage.label's
+ *      numbering; OpenCV, which upstream uses, numbers 8-connected components by 2x2 blocks and can pick the other one on such a tie).
+ * changed[i] = 1 when a component below min_area was met in either pass (also when no pixel differs: a single island below min_area stays
+ * and counts as changed), else 0; area[i] = pixels of the new mask; box_xyxy[4 i ..] = its tight box with inclusive maxima, zeros for an
+ * empty mask.  bits_out may be bits_in.  workspace: device memory of the caller, 256-byte aligned; saber_k_mask_small_regions_bytes(H, W)
+ * bytes hold one mask (8 bytes per pixel, the packed rows and 256 bytes, each rounded up to 256) and the masks are run in passes of as many as
+ * the workspace holds, so it need not grow with n.  A workspace below one mask (the message names the size), min_area < 1, n, H or W below
+ * 1, a null pointer or H * W >= 2^31 is an error (-1, saber_k_last_error) and nothing is written.  13 launches per pass on `stream`; no
+ * synchronisation and no allocation inside. */
+int saber_k_mask_small_regions(const uint32_t* bits_in, int n, int H, int W, int min_area, uint32_t* bits_out, int32_t* changed, int32_t* area,
+                               int32_t* box_xyxy, void* workspace, size_t workspace_bytes, void* stream);
+size_t saber_k_mask_small_regions_bytes(int H, int W);
 /* depth-wise Conv2d(k7, p3) of the memory fuser's ConvNeXt blocks; w (C,1,7,7) */
 int saber_k_dwconv7(const float* in, int H, int W, int C, const float* w, const float* b, float* out, void* stream);
 /* the video predictor's mask_downsample: Conv2d(1, 1, k4, s4) */

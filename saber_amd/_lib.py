@@ -77,6 +77,7 @@ SIGNATURES = {
     "saber_decode_points": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "saber_decode_prompts": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "saber_amg_generate": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(AmgParams), _vp, _i, C.POINTER(MaskMeta), C.POINTER(_i), _vp]),
+    "saber_amg_postprocess_small_regions": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(MaskMeta), _i, _f, _vp, C.POINTER(_i), _vp]),
     "saber_amg_last_syncs": (_i, [_vp]),
     "saber_engine_set_iou_pruning": (_i, [_vp, _i]),
     "saber_engine_set_multipoint": (_i, [_vp, _i]),
@@ -148,6 +149,8 @@ SIGNATURES = {
     "saber_k_merge_max_u16": (_i, [_vp, _vp, C.c_int64, _i, _vp]),
     "saber_k_merge_class_conf": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp]),
     "saber_k_fill_holes": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, C.c_size_t, _vp]),
+    "saber_k_mask_small_regions": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "saber_k_mask_small_regions_bytes": (C.c_size_t, [_i, _i]),
     "saber_k_unpack_masks": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "saber_k_dwconv7": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_dwconv7_t": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -26,6 +26,9 @@ class SAM2AdapterConfig(BaseModel):
     # video path: GiB of device memory for the frame-feature store (16 MiB per frame: a frame of a volume goes through the encoder once,
     # whatever the number of seeds, directions and slabs).  None -> SABER_AMD_VIDEO_STORE_GB, else 0 (off)
     frame_store_gb: Optional[float] = None
+    # mask generator: upstream's min_mask_region_area (postprocess_small_regions: holes and islands below that many pixels leave every
+    # final mask, then a box NMS that prefers untouched masks), on the device.  None -> SABER_AMD_MIN_MASK_REGION_AREA, else 0 (off)
+    min_mask_region_area: Optional[int] = None
     light_modality: bool = False
     amg_cfg: Optional[Any] = None      # cfgAMG instance; None -> cfgAMG() defaults
     min_mask_area: int = 50
@@ -45,6 +48,13 @@ class SAM2AdapterConfig(BaseModel):
     def _check_cfg(cls, v):
         if v not in _TRUNKS:
             raise ValueError(f"cfg must be one of tiny/small/base/large, got '{v}'")
+        return v
+
+    @field_validator("min_mask_region_area")
+    @classmethod
+    def _check_min_mask_region_area(cls, v):
+        if v is not None and v < 0:
+            raise ValueError("min_mask_region_area must be non-negative")
         return v
 
     @field_validator("frame_store_gb")

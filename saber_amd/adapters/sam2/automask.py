@@ -76,17 +76,24 @@ def get_default() -> Dict[str, Any]:
 class EngineMaskGenerator:
     """generate(image) with the contract of sam2.SAM2AutomaticMaskGenerator.generate."""
 
-    def __init__(self, engine, amg_params: Dict[str, Any], max_masks: int = 2048):
+    def __init__(self, engine, amg_params: Dict[str, Any], max_masks: int = 2048, min_mask_region_area: int = 0):
+        """min_mask_region_area: upstream's option of that name (postprocess_small_regions: holes and islands below that many pixels,
+        then a box NMS that prefers untouched masks), on the device; 0 = off: no launch, nothing allocated."""
         from saber_amd.engine import make_amg_params
+        if min_mask_region_area < 0:
+            raise ValueError("min_mask_region_area must be non-negative")
         self.engine = engine
         self.params = make_amg_params(amg_params)
         self.max_masks = max_masks
+        self.min_mask_region_area = int(min_mask_region_area)
 
     @torch.inference_mode()
     def generate_device(self, image):
         """image: (H,W)/(H,W,3) float32 in [0,1], numpy or device tensor -> (bits, meta) on the device."""
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(self.engine.device)
+        if self.min_mask_region_area > 0:
+            return self.engine.amg_generate(image.contiguous(), self.params, max_masks=self.max_masks, min_mask_region_area=self.min_mask_region_area)
         return self.engine.amg_generate(image.contiguous(), self.params, max_masks=self.max_masks)
 
     def generate(self, image) -> List[Dict[str, Any]]:
@@ -102,9 +109,12 @@ class EngineMaskGenerator:
                 for i, m in enumerate(meta)]
 
 
-def build_amg(amg_params: Dict[str, Any], min_mask_area: int, device="cuda", checkpoint: Optional[str] = None):
+def build_amg(amg_params: Dict[str, Any], min_mask_area: int, device="cuda", checkpoint: Optional[str] = None, min_mask_region_area: int = 0):
+    if min_mask_region_area < 0:
+        raise ValueError("min_mask_region_area must be non-negative")
     engine = get_engine(amg_params["sam2_cfg"], device, checkpoint)
-    return fmask.FilteredSAM2MaskGenerator(base_generator=EngineMaskGenerator(engine, amg_params), min_area_filter=min_mask_area)
+    return fmask.FilteredSAM2MaskGenerator(base_generator=EngineMaskGenerator(engine, amg_params, min_mask_region_area=min_mask_region_area),
+                                           min_area_filter=min_mask_area)
 
 
 def amg_cli():

@@ -36,8 +36,19 @@ class SAM2Adapter(BaseAdapter):
                 amg = self._config.amg_cfg.dict()
             else:
                 amg = cfgAMG(sam2_cfg=self._config.cfg).dict()
-            self._mask_generator = build_amg(amg, self._config.min_mask_area, device=self.device, checkpoint=self._config.checkpoint)
+            self._mask_generator = build_amg(amg, self._config.min_mask_area, device=self.device, checkpoint=self._config.checkpoint,
+                                             min_mask_region_area=self._min_mask_region_area())
         return self._mask_generator
+
+    def _min_mask_region_area(self) -> int:
+        """config.min_mask_region_area, else the environment's SABER_AMD_MIN_MASK_REGION_AREA, else 0 (off, upstream's default)"""
+        if self._config.min_mask_region_area is not None:
+            v = int(self._config.min_mask_region_area)
+        else:
+            v = int(os.environ.get("SABER_AMD_MIN_MASK_REGION_AREA") or 0)
+        if v < 0:
+            raise ValueError("min_mask_region_area must be non-negative")
+        return v
 
     @property
     def engine(self):

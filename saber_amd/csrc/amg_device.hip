@@ -55,7 +55,6 @@ __device__ __forceinline__ int block_scan_1024(int flag, int* lds16, int* total)
 
 // Greedy NMS of n candidates already in `cand` (any order), scores in cand[i].score: stable descending order, suppress IoU > thr.
 // order / removed: LDS.  On return keep order is order[a] for the a with removed[a] == 0, ascending a.  n <= AMG_NMS_MAX.
-#define AMG_NMS_MAX 12288
 __device__ void block_nms(const DevCand* __restrict__ cand, int n, float thr, float* s_score, unsigned short* s_order, uint8_t* s_removed) {
     const int tid = threadIdx.x;
     for (int i = tid; i < n; i += 1024) { s_score[i] = cand[i].score; s_removed[i] = 0; }
@@ -274,10 +273,52 @@ const char* launch_box_nms_probe(const float* boxes, const float* scores, int n,
     return nullptr;
 }
 
+// the small-region step behind the clean-up kernels (smallregions.hip): scores from the changed flags, NMS, keep list in NMS order
+__global__ __launch_bounds__(1024) void amg_small_regions_kernel(const int32_t* __restrict__ changed, const int32_t* __restrict__ box, int n, float thr,
+                                                                 DevCand* __restrict__ tmp, int* __restrict__ keep, int* __restrict__ count) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* s_score = reinterpret_cast<float*>(smem);
+    unsigned short* s_order = reinterpret_cast<unsigned short*>(s_score + AMG_NMS_MAX);
+    uint8_t* s_removed = reinterpret_cast<uint8_t*>(s_order + AMG_NMS_MAX);
+    __shared__ int lds16[16];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < n; i += 1024) {
+        DevCand c;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { c.box[q] = (float)box[4 * i + q]; c.crop[q] = 0; }
+        c.iou = c.stab = 0.f; c.pt[0] = c.pt[1] = 0.f; c.area = 0; c.slot = i; c.score = changed[i] ? 0.0f : 1.0f; c.pad = 0;
+        tmp[i] = c;
+    }
+    __threadfence_block();
+    __syncthreads();
+    block_nms(tmp, n, thr, s_score, s_order, s_removed);
+    __syncthreads();
+    int nk = 0;
+    for (int a0 = 0; a0 < n; a0 += 1024) {
+        const int a = a0 + tid;
+        const bool kept = a < n && !s_removed[a];
+        int tot;
+        const int pos = block_scan_1024(kept ? 1 : 0, lds16, &tot);
+        if (kept) keep[nk + pos] = s_order[a];
+        nk += tot;
+    }
+    if (tid == 0) *count = nk;
+}
+const char* launch_small_regions_nms(const int32_t* changed, const int32_t* box_xyxy, int n, float thr, DevCand* tmp, int* keep, int* count,
+                                     const uint32_t* src_bits, uint32_t* out_bits, int64_t words, hipStream_t s) {
+    if (n < 1 || n > AMG_NMS_MAX) return "small_regions: 1 to 12288 masks";
+    hipLaunchKernelGGL(amg_small_regions_kernel, dim3(1), dim3(1024), AMG_NMS_LDS, s, changed, box_xyxy, n, thr, tmp, keep, count);
+    const int64_t per = ((words & 3) == 0 ? words >> 2 : words);
+    hipLaunchKernelGGL(amg_gather_kernel, dim3((unsigned)std::min<int64_t>((per + 255) / 256, 64), n), dim3(256), 0, s, src_bits, (const int*)keep, (const int*)count, n,
+                       out_bits, words);
+    return nullptr;
+}
+
 const char* amg_device_init() {
     hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void*>(amg_crop_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, AMG_NMS_LDS);
     if (st == hipSuccess) st = hipFuncSetAttribute(reinterpret_cast<const void*>(amg_final_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, AMG_NMS_LDS);
     if (st == hipSuccess) st = hipFuncSetAttribute(reinterpret_cast<const void*>(amg_nms_probe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, AMG_NMS_LDS);
+    if (st == hipSuccess) st = hipFuncSetAttribute(reinterpret_cast<const void*>(amg_small_regions_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, AMG_NMS_LDS);
     return st == hipSuccess ? nullptr : hipGetErrorString(st);
 }
 const char* launch_amg_crops(const DevCrop* crops, int n_crops, int max_nm, const MaskStats* stats, const uint8_t* pass, const float* iou, const float* crop_pts, float stab_thr,

@@ -372,6 +372,12 @@ extern "C" int saber_k_fill_holes(const float* in, int n_planes, int H, int W, i
                                   size_t workspace_bytes, void* stream) {
     return kcheck(launch_fill_holes(in, n_planes, H, W, max_area, fill_value, out, workspace, workspace_bytes, (hipStream_t)stream));
 }
+// small holes filled and small islands removed on bit-packed masks (smallregions.hip)
+extern "C" int saber_k_mask_small_regions(const uint32_t* bits_in, int n, int H, int W, int min_area, uint32_t* bits_out, int32_t* changed, int32_t* area,
+                                          int32_t* box_xyxy, void* workspace, size_t workspace_bytes, void* stream) {
+    return kcheck(launch_small_regions(bits_in, n, H, W, min_area, bits_out, changed, area, box_xyxy, workspace, workspace_bytes, (hipStream_t)stream));
+}
+extern "C" size_t saber_k_mask_small_regions_bytes(int H, int W) { return small_regions_bytes_per_mask(H, W); }
 extern "C" int saber_k_add_to_bf16(const float* x, const float* y, int y_rows, uint16_t* out_bf16, float* out_f32, int64_t rows, int C, void* stream) {
     return kcheck(launch_add_to_bf16(x, y, y_rows, out_bf16, out_f32, rows, C, (hipStream_t)stream));
 }

@@ -10,7 +10,8 @@
 //               (ccl_run_start), so x-neighbours are joined before the first atomic
 //   2. merge    the consumer's own kernel: ccl_unite(v, u) for the neighbours u that precede v in scan order, as its connectivity says
 //   3. flatten  parent <- root (ccl_root), after which `lab` is read-only
-//   4. count    voxels per root, at the root's index in `sizes` (one atomic per x-run and 64-voxel chunk)
+//   4. count    voxels per root, at the root's index in `sizes` (one atomic per x-run and 64-voxel chunk; the runs of a row's leading
+//               root are summed and carried along the row: one atomic per row for a component that fills most of it)
 // What makes it safe without locks: a root's entry changes by atomicMin alone (ccl_unite), path halving writes only entries of
 // non-roots and only with an ancestor (ccl_find), so every entry only ever decreases along its own ancestor chain and a chase always
 // ends at a root.  The ballots and shuffles of the row kernels need whole waves: early exits in front of them are wave-uniform.

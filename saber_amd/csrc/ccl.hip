@@ -30,24 +30,40 @@ __global__ __launch_bounds__(256) void ccl_flatten_kernel(uint32_t* __restrict__
     }
 }
 
-// one wave per row; consecutive foreground voxels of a row share their root, so each x-run contributes one atomic per 64-voxel chunk
+// one wave per row.  Consecutive foreground voxels of a row share their root, so an x-run contributes one atomic per 64-voxel chunk -
+// except the runs of the row's LEADING root, which are summed with a ballot and carried from chunk to chunk (pend_root / pend_cnt,
+// wave-uniform) until another root takes the lead or the row ends.  The leading root is the carried one while it still occurs in the
+// chunk, else the root of the chunk's first foreground voxel: a component that fills most of a row (the background of a mask, cut into
+// many runs by specks) then costs the row one atomic instead of one per run, all of which would meet at one address.
 __global__ __launch_bounds__(256) void ccl_count_kernel(const uint32_t* __restrict__ lab, uint32_t* __restrict__ sizes, int W, int64_t rows) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;                                   // wave-uniform
     const int64_t base = row * W;
+    uint32_t pend_root = CCL_NONE, pend_cnt = 0u;
     for (int x0 = 0; x0 < W; x0 += 64) {
         const int x = x0 + lane;
         const uint32_t r = x < W ? lab[base + x] : CCL_NONE;
         const bool fg = r != CCL_NONE;
         const unsigned long long mask = __ballot(fg);
-        const bool head = fg && (lane == 0 || !((mask >> (lane - 1)) & 1ull));
+        if (mask == 0ull) continue;                            // wave-uniform
+        uint32_t lead = pend_root;
+        if (lead == CCL_NONE || __ballot(r == lead) == 0ull) lead = __shfl(r, __ffsll((long long)mask) - 1, 64);
+        const unsigned long long lead_mask = __ballot(r == lead);
+        const bool head = fg && r != lead && (lane == 0 || !((mask >> (lane - 1)) & 1ull));
         if (head) {
             const unsigned long long above_bg = ~mask & ~((2ull << lane) - 1ull);      // background lanes above this one
             const int end = above_bg ? __ffsll((long long)above_bg) - 1 : 64;           // first background lane after the run
             atomicAdd(&sizes[r], (uint32_t)(end - lane));
         }
+        if (lead != pend_root) {
+            if (lane == 0 && pend_root != CCL_NONE) atomicAdd(&sizes[pend_root], pend_cnt);
+            pend_root = lead;
+            pend_cnt = 0u;
+        }
+        pend_cnt += (uint32_t)__popcll(lead_mask);
     }
+    if (lane == 0 && pend_root != CCL_NONE) atomicAdd(&sizes[pend_root], pend_cnt);
 }
 
 template <typename T>

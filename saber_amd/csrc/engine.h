@@ -40,6 +40,8 @@ struct saber_engine {
     void* exact_ws = nullptr;       // exact.hip's workspaces (allocated on first use)
     void* refine_state = nullptr;   // morph3d.hip: ball tables and the pairs of the last saber_refine_membranes call (allocated on first use)
     void* labelstats_ws = nullptr;  // labelstats.hip: label bitmap, rank table and counters (1 MiB, allocated on first use, freed with allocs)
+    void* sr_ws = nullptr; size_t sr_ws_bytes = 0;                 // smallregions.hip: labels, sizes, intermediate rows and records of one chunk of masks (bounded: SR_WS_BUDGET)
+    void* sr_stage = nullptr; size_t sr_stage_bytes = 0;           // smallregions.hip: the cleaned packed rows of a call's masks, its results and NMS candidates (grown on demand, freed with allocs)
     void* consensus_ws = nullptr; size_t consensus_ws_bytes = 0;   // consensus2d.hip: per-pixel averages, root bitmap, rank table, selection (grown on demand, freed with allocs)
 
     // model description (tiny / small / base+ / large)

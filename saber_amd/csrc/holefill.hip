@@ -60,6 +60,10 @@ __global__ __launch_bounds__(256) void hf_merge_kernel(uint32_t* lab, int H, int
     }
 }
 
+void ccl8_merge_planes(uint32_t* lab, int H, int W, int64_t n, unsigned blocks, hipStream_t s) {
+    hipLaunchKernelGGL(hf_merge_kernel, dim3(blocks), dim3(256), 0, s, lab, H, W, n);
+}
+
 __global__ __launch_bounds__(256) void hf_write_kernel(const uint32_t* in, const uint32_t* __restrict__ lab, const uint32_t* __restrict__ sizes,
                                                        uint32_t max_area, uint32_t fill_bits, uint32_t* out, int64_t n) {
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
@@ -83,7 +87,7 @@ const char* launch_fill_holes(const float* in, int n_planes, int H, int W, int m
     union { float f; uint32_t u; } fill;
     fill.f = fill_value;
     hipLaunchKernelGGL(hf_init_kernel, dim3(row_blocks), dim3(256), 0, s, (const uint32_t*)in, lab, sizes, W, rows);
-    if (H > 1) hipLaunchKernelGGL(hf_merge_kernel, dim3(px_blocks), dim3(256), 0, s, lab, H, W, n);
+    if (H > 1) ccl8_merge_planes(lab, H, W, n, px_blocks, s);
     ccl_flatten(lab, n, px_blocks, s);
     ccl_count(lab, sizes, W, rows, s);
     hipLaunchKernelGGL(hf_write_kernel, dim3(px_blocks), dim3(256), 0, s, (const uint32_t*)in, (const uint32_t*)lab, (const uint32_t*)sizes,

@@ -106,6 +106,15 @@ const char* launch_merge_class_conf(uint16_t* fin, float* best, const uint16_t* 
 // workspace: n_planes * H * W * 8 bytes (labels, sizes); out may be in; five launches on s, no synchronisation
 const char* launch_fill_holes(const float* in, int n_planes, int H, int W, int max_area, float fill_value, float* out, void* workspace,
                               size_t workspace_bytes, hipStream_t s);
+// rows of `lab` (n entries, planes of H rows) against the row above, 8-connected, never across planes or row ends: the merge step of ccl.h
+// for planes whose members are the entries != CCL_NONE (holefill.hip; shared with smallregions.hip)
+void ccl8_merge_planes(uint32_t* lab, int H, int W, int64_t n, unsigned blocks, hipStream_t s);
+// ------------------------------------------------------------------ smallregions.hip: small holes filled, small islands removed, on bit-packed masks
+// in / out: (n,H,W32) uint32 rows (out may be in); changed, area: n int32; box_xyxy: 4 n int32 (inclusive maxima, zeros for an empty mask).
+// workspace: 256-byte aligned, at least small_regions_bytes_per_mask(H, W); the masks are run in passes of as many as it holds.
+size_t small_regions_bytes_per_mask(int H, int W);
+const char* launch_small_regions(const uint32_t* in, int n, int H, int W, int min_area, uint32_t* out, int32_t* changed, int32_t* area, int32_t* box_xyxy,
+                                 void* workspace, size_t workspace_bytes, hipStream_t s);
 const char* launch_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res,
                                     hipStream_t s);
 const char* launch_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images,
@@ -174,7 +183,13 @@ struct MaskStats { int area; int inter; int uni; int x0; int y0; int x1; int y1;
 struct DevCand { float box[4]; float iou, stab; float pt[2]; int crop[4]; int area; int slot; float score; int pad; };   // slot: index of the bit mask in the K8 scratch
 struct DevCrop { int box[4]; int kbase; int nm; int pt0; int M; };   // one crop of a decoded batch: first candidate / candidates / first grid point (batch-relative), masks per point
 struct saber_mask_meta;
+#define AMG_NMS_MAX 12288      // candidates one workgroup's NMS holds in LDS
 const char* amg_device_init();
+// The tail of the small-region step (smallregions.hip): score 1 for an untouched mask and 0 for a changed one, greedy box NMS (IoU > thr) in
+// stable descending score order, the survivors' indices in that order -> keep[0 .. *count), and out_bits row i = src_bits row keep[i].
+// changed: n, box_xyxy: 4 n int32; tmp: n candidates; n <= AMG_NMS_MAX; out_bits must not overlap src_bits
+const char* launch_small_regions_nms(const int32_t* changed, const int32_t* box_xyxy, int n, float thr, DevCand* tmp, int* keep, int* count,
+                                     const uint32_t* src_bits, uint32_t* out_bits, int64_t words, hipStream_t s);
 const char* launch_box_nms_probe(const float* boxes, const float* scores, int n, float thr, void* tmp /* n x 64 bytes */, int* keep, int* count, hipStream_t s);
 const char* launch_amg_plane(const float* iou, const int* sel, int n, int plane_mode, float thr, int* plane, uint8_t* pass, hipStream_t s);
 const char* launch_amg_crops(const DevCrop* crops, int n_crops, int max_nm, const MaskStats* stats, const uint8_t* pass, const float* iou, const float* crop_pts, float stab_thr,

@@ -200,8 +200,16 @@ class Engine:
         return low, iou, obj
 
     # ------------------------------------------------------------------ AMG
-    def amg_generate(self, img: torch.Tensor, params: "_lib.AmgParams", max_masks: int = 1024):
-        """img: (H,W) or (H,W,3) float32 in [0,1].  Returns (bits uint32 (n,H,W32) device tensor, list of MaskMeta)."""
+    def amg_generate(self, img: torch.Tensor, params: "_lib.AmgParams", max_masks: int = 1024, min_mask_region_area: int = 0):
+        """img: (H,W) or (H,W,3) float32 in [0,1].  Returns (bits uint32 (n,H,W32) device tensor, list of MaskMeta).
+        min_mask_region_area > 0: upstream's option of that name - postprocess_small_regions on the final masks with the NMS threshold
+        max(params.box_nms_thresh, params.crop_nms_thresh); 0 (default) = off: no launch, nothing allocated."""
+        if min_mask_region_area < 0:
+            raise ValueError("min_mask_region_area must be non-negative")
+        if min_mask_region_area > 0:
+            bits, meta = self.amg_generate(img, params, max_masks=max_masks)
+            return self.postprocess_small_regions(bits, meta, img.shape[0], img.shape[1], min_mask_region_area,
+                                                  max(params.box_nms_thresh, params.crop_nms_thresh))
         assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous()
         H, W = img.shape[:2]
         ch = 1 if img.dim() == 2 else img.shape[2]
@@ -226,6 +234,64 @@ class Engine:
         self._check(st)
         n = cnt.value
         return bits[:n], [meta[i] for i in range(n)]
+
+    # ------------------------------------------------------------------ small regions (csrc/smallregions.hip)
+    SMALL_REGIONS_WS_BYTES = 128 << 20      # label workspace of remove_small_regions: the masks are run in passes of as many as it holds
+
+    def _check_packed(self, who: str, bits, W: int):
+        if not isinstance(bits, torch.Tensor) or not bits.is_cuda:
+            raise ValueError(f"{who}: the mask stack must be a device tensor")
+        if bits.dtype not in (torch.int32, torch.uint32) or bits.dim() != 3 or bits.shape[2] != (int(W) + 31) // 32 or int(W) < 1:
+            raise ValueError(f"{who}: the mask stack must be (n,H,ceil(W/32)) int32 for W = {W}, got {tuple(bits.shape)} {bits.dtype}")
+        if bits.device != self.device:
+            raise ValueError(f"{who}: the mask stack is on {bits.device}, the engine on {self.device}")
+        return bits.contiguous()
+
+    def remove_small_regions(self, bits: torch.Tensor, W: int, min_area: int):
+        """Holes, then islands, of fewer than min_area pixels (8-connected) of every mask of a bit-packed (n,H,W32) int32 device stack
+        (include/saber_amd_kernels.h: saber_k_mask_small_regions).  Returns device tensors (bits_out (n,H,W32), changed (n,) int32 0/1,
+        area (n,) int32, boxes (n,4) int32 [x0,y0,x1,y1] with inclusive maxima); the input is left as it is.  No host synchronisation."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("saber_amd.Engine.remove_small_regions needs a ROCm device; there is no CPU fallback")
+        bits = self._check_packed("remove_small_regions", bits, W)
+        if min_area < 1:
+            raise ValueError("remove_small_regions: min_area must be at least 1")
+        n, H = int(bits.shape[0]), int(bits.shape[1])
+        out = torch.empty_like(bits)
+        changed = torch.empty((n,), dtype=torch.int32, device=self.device)
+        area = torch.empty((n,), dtype=torch.int32, device=self.device)
+        boxes = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        if n == 0 or H == 0:
+            return out, changed, area, boxes
+        per = int(self.lib.saber_k_mask_small_regions_bytes(H, int(W)))
+        ws = torch.empty((per * max(1, min(n, self.SMALL_REGIONS_WS_BYTES // per)),), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            if self.lib.saber_k_mask_small_regions(_ptr(bits), n, H, int(W), int(min_area), _ptr(out), _ptr(changed), _ptr(area), _ptr(boxes), _ptr(ws),
+                                                   ws.numel(), _stream()) != 0:
+                raise ValueError(f"saber_amd: {self.lib.saber_k_last_error().decode()}")
+        return out, changed, area, boxes
+
+    def postprocess_small_regions(self, bits: torch.Tensor, meta, H: int, W: int, min_area: int, nms_thresh: float):
+        """SAM2AutomaticMaskGenerator.postprocess_small_regions on what amg_generate returned (include/saber_amd.h:
+        saber_amg_postprocess_small_regions): small holes filled and small islands removed per mask, box NMS that prefers untouched
+        masks, survivors in NMS order.  bits: (n,H,W32) int32 device tensor, meta: its n MaskMeta records.  Returns (bits, meta) like
+        amg_generate; the inputs are left as they are.  One host synchronisation."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("saber_amd.Engine.postprocess_small_regions needs a ROCm device; there is no CPU fallback")
+        bits = self._check_packed("postprocess_small_regions", bits, W)
+        n = int(bits.shape[0])
+        if len(meta) != n or int(bits.shape[1]) != int(H):
+            raise ValueError(f"postprocess_small_regions: {len(meta)} records and H = {H} for a stack of {tuple(bits.shape)}")
+        if n == 0:
+            return bits, []
+        rec = (_lib.MaskMeta * n)()
+        for i, m in enumerate(meta):
+            C.memmove(C.byref(rec[i]), C.byref(m), C.sizeof(_lib.MaskMeta))
+        out = torch.empty_like(bits)
+        cnt = C.c_int(0)
+        self._check(self.lib.saber_amg_postprocess_small_regions(self.h, _ptr(bits), n, int(H), int(W), rec, int(min_area), float(nms_thresh), _ptr(out),
+                                                                 C.byref(cnt), _stream()))
+        return out[:cnt.value], [rec[i] for i in range(cnt.value)]
 
     def label_plane(self, bits: torch.Tensor, order: Sequence[int], H: int, W: int) -> torch.Tensor:
         plane = torch.empty((H, W), dtype=torch.uint16, device=self.device)

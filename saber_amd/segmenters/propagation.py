@@ -144,6 +144,7 @@ class propagationSegmenter(saber3D):
         from saber_amd.segmenters.slice_driver import segment_slice_to_plane, segment_volume_sharded
         gen = self.adapter._generator()
         eng, params = gen.base_generator.engine, gen.base_generator.params
+        region_area = getattr(gen.base_generator, "min_mask_region_area", 0)       # the adapter's small-region clean-up, per slice
         engines = [eng]
         if handles_per_gpu > 1:
             # replicas of the PRIMARY engine's model (the adapter's own `cfg` field may name another trunk)
@@ -165,7 +166,8 @@ class propagationSegmenter(saber3D):
                     sl = torch.from_numpy(np.ascontiguousarray(sl if sl.dtype == np.uint16 else sl.astype(np.float32))).to(engine.device)
                 plane, _ = segment_slice_to_plane(engine, sl, params, min_mask_area=self.min_mask_area,
                                                   remove_repeating_masks=self.remove_repeating_masks, max_masks=gen.base_generator.max_masks,
-                                                  classifier=classifier, target_class=1, classifier_min_area=self.batchsize)
+                                                  classifier=classifier, target_class=1, classifier_min_area=self.batchsize,
+                                                  **({"min_mask_region_area": region_area} if region_area > 0 else {}))
                 return plane
             return one
 
