@@ -150,6 +150,14 @@ int saber_k_dwconv7_t_batched(const float* in, int64_t in_stride, int H, int W, 
 int saber_k_conv4x4s4(const float* in, int H, int W, const float* w, const float* b, float* out, void* stream);
 /* F.interpolate(mode="bilinear", align_corners=False, antialias) of n planes, fused post transform: 0 none, 1 a*sigmoid(v)+c, 2 a*(v>0)+c, 3 a*v+c, 4 (v>=a) */
 int saber_k_resize_plane(const float* in, int n_planes, int H, int W, float* out, int Ho, int Wo, int antialias, int post, float a, float c, void* stream);
+/* saber_k_resize_plane(antialias 0, post 0) of the n_planes contiguous (H,W) planes of one video frame - its objects, in obj_ids order - with
+ * upstream's non-overlapping constraint (SAM2Base non_overlap_masks: _apply_non_overlapping_constraints on the video-resolution logits) applied
+ * in the same launch.  With v[i] the bits saber_k_resize_plane writes for plane i at a pixel: out[i] = v[i] for the first i that attains
+ * max_i v[i] (torch.argmax), out[i] = min(v[i], suppress_max) for every other plane (torch.clamp(max=-10.0): suppress_max is -10).
+ * n_planes = 1 is the plain resize, n_planes = 0 returns 0 without a launch; any number of planes is served by one launch.  A null pointer,
+ * n_planes < 0, a side below 1 or an input side above 2^22 is an error (-1, saber_k_last_error) answered before any launch.  Inputs are finite.
+ * out must not overlap in.  No synchronisation and no allocation inside. */
+int saber_k_resize_planes_non_overlap(const float* in, int n_planes, int H, int W, float* out, int Ho, int Wo, float suppress_max, void* stream);
 /* MXFP8 GEMM on the block-scaled MFMA v_mfma_scale_f32_16x16x128_f8f6f4 (row g-1): out = act(A . W^T + bias) (+ res).  Operands in the OCP MX
  * format: e4m3fn elements ([M][lda] / [N][ldw] bytes, K contiguous, zero-padded to Kp, a multiple of 128) + one e8m0 scale byte per 32
  * K-elements, stored K-step-major: S[Kp / 128][rows][4] (rows >= the operand's rows rounded up to whole tiles: a multiple of 768 for A, of 192 for W).

@@ -158,6 +158,7 @@ SIGNATURES = {
     "saber_k_dwconv7_t_batched": (_i, [_vp, C.c_int64, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _i, _vp]),
     "saber_k_conv4x4s4": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_resize_plane": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _vp]),
+    "saber_k_resize_planes_non_overlap": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _f, _vp]),
     "saber_k_box_nms": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     "saber_k_gemm_mx": (_i, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _i, _i, _i, _vp]),
     "saber_k_quant_mx": (_i, [_vp, C.c_int64, _i, _vp, C.c_int64, _i, _vp, C.c_int64, C.c_int64, _vp]),

@@ -26,6 +26,10 @@ class SAM2AdapterConfig(BaseModel):
     # video path: GiB of device memory for the frame-feature store (16 MiB per frame: a frame of a volume goes through the encoder once,
     # whatever the number of seeds, directions and slabs).  None -> SABER_AMD_VIDEO_STORE_GB, else 0 (off)
     frame_store_gb: Optional[float] = None
+    # video path: upstream SAM2's non_overlap_masks - at every pixel of the video-resolution logits a frame hands out, the object with the
+    # highest logit (the first of them on a tie) keeps its value and the others are clamped to at most -10, so overlapping objects are
+    # painted by confidence and not by paint order.  None -> SABER_AMD_NON_OVERLAP_MASKS=1, else off
+    non_overlap_masks: Optional[bool] = None
     # mask generator: upstream's min_mask_region_area (postprocess_small_regions: holes and islands below that many pixels leave every
     # final mask, then a box NMS that prefers untouched masks), on the device.  None -> SABER_AMD_MIN_MASK_REGION_AREA, else 0 (off)
     min_mask_region_area: Optional[int] = None

@@ -78,7 +78,7 @@ class SAM2Adapter(BaseAdapter):
             eng = get_engine(self._config.cfg, self.device, self._config.checkpoint, max_images=16, max_prompts=8, replica=1000, multipoint=True)
             W = pretrained_weights.load_weights(self._config.cfg, self._config.checkpoint, video=True)
             self._video_predictor = VideoPredictor(eng, W, num_maskmem=self._config.num_maskmem, fill_hole_area=self._fill_hole_area(),
-                                                   frame_store_gb=self._config.frame_store_gb)
+                                                   frame_store_gb=self._config.frame_store_gb, non_overlap_masks=self._config.non_overlap_masks)
         return self._video_predictor
 
     def _fill_hole_area(self) -> int:
@@ -144,7 +144,7 @@ class SAM2Adapter(BaseAdapter):
     @torch.inference_mode()
     def segment_volume(self, start_frame_idx: int, masks=None, vol_shape=None, max_frame_num_to_track=None,
                        min_presence_score: float = 0.5, inference_state=None, *, device_volume: bool = False,
-                       batch_objects: Optional[bool] = None):
+                       batch_objects: Optional[bool] = None, non_overlap_masks: Optional[bool] = None):
         """Bidirectional propagation + presence-score filter, predictor.py:232-348 step by step.  The reference captures the mask decoder's
         object-score logits with a forward hook and files them under `_current_frame`, which it updates only AFTER the generator has
         yielded a frame: a frame's scores therefore land on the frame yielded before it.  Reproduced as is (it feeds the boundary fit).
@@ -152,7 +152,12 @@ class SAM2Adapter(BaseAdapter):
         per frame for all its objects, the presence filter as one (Z, n + 1) table look-up - and comes back as the (Z,H,W) int16 tensor
         of uint16 values Engine.separate_masks accepts; frame_metrics and frame_scores are filled as on the host route.
         batch_objects=True / False: the memory attention of all objects of a frame as one set of launches, or object by object, for this
-        call (VideoPredictor.batch_objects; same bits either way); None keeps the video predictor's own setting (SABER_AMD_VIDEO_BATCH)."""
+        call (VideoPredictor.batch_objects; same bits either way); None keeps the video predictor's own setting (SABER_AMD_VIDEO_BATCH).
+        non_overlap_masks=True / False: upstream's option of that name for this call (VideoPredictor.non_overlap_masks): the yielded logits
+        have at most one object above -10 at a pixel, so where seeds or tracked masks overlap the voxel gets the id of the object with the
+        highest logit (the lowest id on a tie, as on the seeded frame, where seeds tie at +10) instead of the highest id painted last;
+        frame_scores and everything the tracker stores are the same.  None keeps the predictor's own setting (SAM2AdapterConfig /
+        SABER_AMD_NON_OVERLAP_MASKS)."""
         from saber_amd.filters.estimate_thickness import fit_organelle_boundaries
         if device_volume:
             from saber_amd.utils import labelvol, volprep
@@ -172,6 +177,9 @@ class SAM2Adapter(BaseAdapter):
         was_batched = state.batch_objects
         if batch_objects is not None:
             state.batch_objects = bool(batch_objects)
+        was_non_overlap = state.non_overlap_masks
+        if non_overlap_masks is not None:
+            state.non_overlap_masks = bool(non_overlap_masks)
         try:
             for obj_id, mask in enumerate(mask_list, start=1):
                 if np.max(mask) == 0:
@@ -214,6 +222,7 @@ class SAM2Adapter(BaseAdapter):
         finally:
             state.hook = None
             state.batch_objects = was_batched
+            state.non_overlap_masks = was_non_overlap
         n_masks = len(mask_list)
         if n_masks > 0:
             frame_scores = np.zeros([Z, n_masks])

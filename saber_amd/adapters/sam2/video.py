@@ -21,6 +21,10 @@ of the object score) - the decisions upstream also takes on the host.  Objects a
 Settings follow the sam2.1 configs and the reference's construction (num_maskmem truncated to SAM2AdapterConfig.num_maskmem = 2,
 predictor.py:28-34).  Upstream's hole filling (fill_holes_in_mask_scores on the low-resolution logits after every single-frame inference;
 its default fill_hole_area is 8 where its CUDA extension is built) is VideoPredictor(fill_hole_area=...): saber_k_fill_holes, off (0) by default.
+Upstream's non_overlap_masks (_apply_non_overlapping_constraints on the video-resolution logits of every output: at each pixel the first
+object with the highest logit keeps its value, the others are clamped to at most -10) is VideoPredictor(non_overlap_masks=True): the resize of
+a frame's planes and the constraint are one launch, saber_k_resize_planes_non_overlap (_video_logits); off by default, and nothing that is
+stored changes.  non_overlap_masks_for_mem_enc does nothing under upstream's per-object inference (batch 1) and has no counterpart here.
 """
 import ctypes as C
 import math
@@ -233,7 +237,8 @@ class VideoPredictor:
     """add_new_mask / propagate_in_video of the SAM2 video predictor on one engine handle."""
 
     def __init__(self, engine, weights: Dict[str, np.ndarray], num_maskmem: int = 2, batch_objects: Optional[bool] = None, object_batch: int = 16,
-                 fill_hole_area: int = 0, batch_tail: Optional[bool] = None, frame_store_gb: Optional[float] = None):
+                 fill_hole_area: int = 0, batch_tail: Optional[bool] = None, frame_store_gb: Optional[float] = None,
+                 non_overlap_masks: Optional[bool] = None):
         """batch_objects: the memory attention of all objects that are tracked on a frame runs as one set of launches
         (_memory_conditioned_batch; bit-identical to the per-object route); None = the environment switch SABER_AMD_VIDEO_BATCH=1, else off.
         object_batch: most objects per batch (bounds the workspace and activations: ~0.1 GB per object)
@@ -251,7 +256,13 @@ class VideoPredictor:
         (no eviction): a window with a frame that is neither stored nor can get a row is encoded as a whole, as without the store.  The
         store outlives reset_state(), and init_state() with frames bit-equal to the loaded ones; drop_frame_store() frees it.  Same bits as
         without it.  Bypassed while window encodes shard over ranks (_ranks()[0] > 1).  None = the environment's SABER_AMD_VIDEO_STORE_GB,
-        else 0 = off: no launch, nothing allocated."""
+        else 0 = off: no launch, nothing allocated.
+        non_overlap_masks: upstream's setting of the same name: in every stack of video-resolution logits this class hands out (the yields of
+        propagate_in_video, _frame_output) at most one object stays above -10 at a pixel - the first one, in obj_ids order, with the highest
+        logit keeps its value, every other one reads min(value, -10) (_video_logits: the resize and the constraint in one launch).  Applied
+        after fill_hole_area, to the outputs alone: memories, object pointers and the stored pred_masks are those of a run without it.
+        None = the environment switch SABER_AMD_NON_OVERLAP_MASKS=1, else off: no new launch, nothing allocated, the outputs as before."""
+        self.non_overlap_masks = os.environ.get("SABER_AMD_NON_OVERLAP_MASKS", "0") not in ("", "0") if non_overlap_masks is None else bool(non_overlap_masks)
         if fill_hole_area < 0:
             raise ValueError("fill_hole_area must be non-negative")
         self.fill_hole_area = int(fill_hole_area)
@@ -777,8 +788,18 @@ class VideoPredictor:
 
     def _frame_output(self, frame_idx: int):
         """(frame_idx, obj_ids, video-resolution mask logits (n_obj,1,Hv,Wv)) of the frame as the state holds it now: an object without an
-        output on the frame reads NO_OBJ_SCORE, like upstream's consolidated outputs."""
+        output on the frame reads NO_OBJ_SCORE, like upstream's consolidated outputs.  With non_overlap_masks the constraint runs over the
+        objects that have an output (_video_logits) and the absent ones are put between them as constant planes: a plane of NO_OBJ_SCORE
+        lies below -10, so the clamp leaves it as it is whether it wins or loses, and it wins only where every present object is below it,
+        where the clamp leaves those unchanged too - the stack is what the constraint over all n planes gives."""
         Hv, Wv = self.video_hw
+        if self.non_overlap_masks:
+            held = [self.temp[oid].get(frame_idx) or self.out[oid]["cond"].get(frame_idx) or self.out[oid]["non_cond"].get(frame_idx) for oid in self.obj_ids]
+            at = [i for i, o in enumerate(held) if o is not None]
+            masks = torch.full((len(held), 1, Hv, Wv), self.NO_OBJ_SCORE, dtype=torch.float32, device=self.dev)
+            if at:
+                masks[at, 0] = self._video_logits(torch.stack([held[i]["pred_masks"] for i in at], 0), Hv, Wv)
+            return frame_idx, list(self.obj_ids), masks
         outs = []
         for oid in self.obj_ids:
             o = self.temp[oid].get(frame_idx) or self.out[oid]["cond"].get(frame_idx) or self.out[oid]["non_cond"].get(frame_idx)
@@ -1152,6 +1173,18 @@ class VideoPredictor:
         self._ck(self.lib.saber_k_resize_plane(self._p(planes), n, 256, 256, self._p(out), Hv, Wv, 0, 0, 0.0, 0.0, self._s()))
         return out
 
+    def _video_logits(self, planes: torch.Tensor, Hv: int, Wv: int) -> torch.Tensor:
+        """The video-resolution logits (n,Hv,Wv) of a frame from the (n,256,256) stack of its objects' low-resolution logits, in obj_ids
+        order.  With non_overlap_masks: _resize_planes and upstream's _apply_non_overlapping_constraints in one launch - at every pixel
+        the first object with the highest resized logit keeps it, every other one reads min(its own, -10).  Else _resize_planes."""
+        if not self.non_overlap_masks:
+            return self._resize_planes(planes, Hv, Wv)
+        planes = planes.contiguous()
+        n = planes.shape[0]
+        out = self._new(n, Hv, Wv)
+        self._ck(self.lib.saber_k_resize_planes_non_overlap(self._p(planes), n, 256, 256, self._p(out), Hv, Wv, -10.0, self._s()))
+        return out
+
     @torch.inference_mode()
     def propagate_in_video(self, start_frame_idx: int, max_frame_num_to_track: Optional[int] = None, reverse: bool = False) -> Iterator:
         """yields (frame_idx, obj_ids, video_res_mask_logits (n_obj, 1, Hv, Wv) device fp32) like upstream"""
@@ -1186,7 +1219,7 @@ class VideoPredictor:
                         if stack is None or len(todo) != len(self.obj_ids):       # with the planes of the objects this frame is a conditioning frame of
                             stack = torch.stack([(self.out[oid]["cond"][t] if t in self.out[oid]["cond"] else self.out[oid]["non_cond"][t])["pred_masks"]
                                                  for oid in self.obj_ids], 0)
-                        yield t, list(self.obj_ids), self._resize_planes(stack, Hv, Wv)[:, None]
+                        yield t, list(self.obj_ids), self._video_logits(stack, Hv, Wv)[:, None]
                         continue
                     conds = dict(zip(todo, rows))
             for oid in self.obj_ids:
@@ -1201,5 +1234,8 @@ class VideoPredictor:
                     o = self._track(oid, t, reverse)
                     self.out[oid]["non_cond"][t] = o
                     low = o["pred_masks"]
-                outs.append(self._resize(low, 256, 256, Hv, Wv))
+                outs.append(low if self.non_overlap_masks else self._resize(low, 256, 256, Hv, Wv))
+            if self.non_overlap_masks:       # the constraint reads all of the frame's objects: their planes as one stack, one launch
+                yield t, list(self.obj_ids), self._video_logits(torch.stack(outs, 0), Hv, Wv)[:, None]
+                continue
             yield t, list(self.obj_ids), torch.stack(outs, 0)[:, None]

@@ -312,6 +312,10 @@ extern "C" int saber_k_conv4x4s4(const float* in, int H, int W, const float* w, 
 extern "C" int saber_k_resize_plane(const float* in, int n_planes, int H, int W, float* out, int Ho, int Wo, int antialias, int post, float a, float c, void* stream) {
     return kcheck(launch_resize_plane(in, n_planes, H, W, out, Ho, Wo, antialias, post, a, c, (hipStream_t)stream));
 }
+extern "C" int saber_k_resize_planes_non_overlap(const float* in, int n_planes, int H, int W, float* out, int Ho, int Wo, float suppress_max, void* stream) {
+    if (const char* m = launch_resize_planes_non_overlap(in, n_planes, H, W, out, Ho, Wo, suppress_max, (hipStream_t)stream)) return kfail(m);
+    return n_planes == 0 ? 0 : kcheck(nullptr);
+}
 extern "C" int saber_k_gemm_mx(const uint8_t* A, int64_t lda, const uint8_t* SA, int64_t sa_rows, const uint8_t* W, int64_t ldw, const uint8_t* SW, int64_t sw_rows, const float* bias,
                                const float* res, float* out_f32, uint16_t* out_bf16, uint8_t* out_mx, uint8_t* out_mx_scales, int64_t out_mx_rows, int64_t ldc, int64_t M, int N, int Kp,
                                int act, void* stream) {

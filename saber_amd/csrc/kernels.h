@@ -226,6 +226,7 @@ SABER_OP_FWD(launch_prompt_tokens16) SABER_OP_FWD(launch_dec_tokens16) SABER_OP_
 SABER_OP_FWD(launch_mask_post) SABER_OP_FWD(launch_gather_masks) SABER_OP_FWD(launch_label_plane) SABER_OP_FWD(launch_pair_intersections) SABER_OP_FWD(launch_unpermute_nchw)
 SABER_OP_FWD(launch_rope) SABER_OP_FWD(launch_softmax_rows) SABER_OP_FWD(launch_conv3x3s2) SABER_OP_FWD(launch_unpack_masks) SABER_OP_FWD(launch_paint_nearest)
 SABER_OP_FWD(launch_conv3x3s2_t) SABER_OP_FWD(launch_dwconv7_t) SABER_OP_FWD(launch_dwconv7) SABER_OP_FWD(launch_conv4x4s4) SABER_OP_FWD(launch_resize_plane)
+SABER_OP_FWD(launch_resize_planes_non_overlap)
 SABER_OP_FWD(launch_flash256) SABER_OP_FWD(launch_gauss_mirror) SABER_OP_FWD(launch_axpy) SABER_OP_FWD(launch_bf16_to_f32)
 SABER_OP_FWD(launch_rope_batched) SABER_OP_FWD(launch_flash256_batched) SABER_OP_FWD(launch_membank_assemble)
 SABER_OP_FWD(launch_conv3x3s2_t_batched) SABER_OP_FWD(launch_dwconv7_t_batched)

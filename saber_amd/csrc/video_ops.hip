@@ -518,6 +518,106 @@ const char* launch_resize_plane(const float* in, int n_planes, int H, int W, flo
     return nullptr;
 }
 
+// ------------------------------------------------------------------------------------------------ plane resize + non-overlapping masks
+// Upstream's _apply_non_overlapping_constraints (SAM2Base, non_overlap_masks) behind the bilinear resize of a frame's objects, in one pass:
+// with v[i] = what resize_plane_kernel (antialias 0, post 0) writes for plane i at a pixel, bit for bit, the first maximal plane keeps its
+// value (torch.argmax: strict > from plane 0) and every other plane gets min(v[i], suppress_max).  A thread owns VEC contiguous pixels of a
+// row: their taps and normalised weights are computed once and serve every plane (the per-plane kernel recomputes them n times), one loop
+// over the planes finds the winner, a second one recomputes the values (the 256 KiB source planes stay in L2) and stores them.
+// Without the antialias filter the support is 1, so a pixel has at most 3 taps per axis while centre + 1.5 is exact to well below 1, which the
+// launcher's bound on the input sides guarantees; a tap beyond n has weight 0 and is not read.
+// Floating-point contraction is spelled out, so that the bits do not depend on how this kernel happens to be compiled: contraction is off in
+// the two functions below, and what the compiler fuses in resize_plane_kernel is written as a fused multiply-add - centre -+ support in the
+// tap range (the centre the weights use is the rounded product), `row += w * v` and `acc += wy * row`.
+struct RWeights { int lo; int n; float w[3]; };
+__device__ __forceinline__ RWeights rweights(int o, int in_size, int out_size) {      // rtaps(o, in_size, out_size, 0) and the weights w[j] / sum of its taps
+#pragma clang fp contract(off)
+    const float scale = (float)in_size / (float)out_size;
+    const float x = (float)o + 0.5f;
+    const float center = scale * x;
+    RWeights r;
+    r.lo = max((int)(__fmaf_rn(scale, x, -1.0f) + 0.5f), 0);
+    r.n = min(min((int)(__fmaf_rn(scale, x, 1.0f) + 0.5f), in_size) - r.lo, 3);
+    float t[3], sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        t[j] = j < r.n ? rtri((float)(j + r.lo) - center + 0.5f) : 0.f;
+        sum += t[j];                                             // + 0 beyond n: the sum over the n taps
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r.w[j] = t[j] / sum;
+    return r;
+}
+__device__ __forceinline__ float rsample(const float* __restrict__ ip, int W, const RWeights& ty, const RWeights& tx) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+#pragma unroll
+    for (int jy = 0; jy < 3; ++jy) {
+        if (jy < ty.n) {
+            const float* rp = ip + (int64_t)(ty.lo + jy) * W + tx.lo;
+            float row = 0.f;
+#pragma unroll
+            for (int jx = 0; jx < 3; ++jx)
+                if (jx < tx.n) row = __fmaf_rn(tx.w[jx], rp[jx], row);
+            acc = __fmaf_rn(ty.w[jy], row, acc);
+        }
+    }
+    return acc;
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void resize_planes_non_overlap_kernel(const float* __restrict__ in, int n_planes, int H, int W, float* __restrict__ out,
+                                                                        int Ho, int Wo, float suppress_max) {
+    const int64_t in_stride = (int64_t)H * W, out_stride = (int64_t)Ho * Wo;
+    const int64_t groups = out_stride / VEC;                      // VEC divides Wo
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+        const int64_t idx = g * VEC;
+        const int ox = (int)(idx % Wo), oy = (int)(idx / Wo);
+        const RWeights ty = rweights(oy, H, Ho);
+        RWeights tx[VEC];
+        float best[VEC];
+        int win[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            tx[k] = rweights(ox + k, W, Wo);
+            best[k] = rsample(in, W, ty, tx[k]);
+            win[k] = 0;
+        }
+        for (int i = 1; i < n_planes; ++i) {
+            const float* ip = in + i * in_stride;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float v = rsample(ip, W, ty, tx[k]);
+                if (v > best[k]) { best[k] = v; win[k] = i; }     // strictly: the first maximal plane wins a tie
+            }
+        }
+        for (int i = 0; i < n_planes; ++i) {
+            const float* ip = in + i * in_stride;
+            float v[VEC];
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float x = rsample(ip, W, ty, tx[k]);
+                v[k] = i == win[k] ? x : fminf(x, suppress_max);
+            }
+            float* op = out + i * out_stride + idx;
+            if constexpr (VEC == 4) *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
+            else op[0] = v[0];
+        }
+    }
+}
+const char* launch_resize_planes_non_overlap(const float* in, int n_planes, int H, int W, float* out, int Ho, int Wo, float suppress_max, hipStream_t s) {
+    if (!in || !out) return "resize_planes_non_overlap: null pointer";
+    if (n_planes < 0) return "resize_planes_non_overlap: n_planes must not be negative";
+    if (H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return "resize_planes_non_overlap: empty plane";
+    if (H > (1 << 22) || W > (1 << 22)) return "resize_planes_non_overlap: input sides above 2^22 are not supported";
+    if (n_planes == 0) return nullptr;
+    const int64_t total = (int64_t)Ho * Wo;
+    if ((Wo & 3) == 0 && ((uintptr_t)out & 15u) == 0)           // 16-byte stores: rows and planes then start on 16 bytes as well
+        hipLaunchKernelGGL(resize_planes_non_overlap_kernel<4>, dim3(grid_for(total / 4)), dim3(256), 0, s, in, n_planes, H, W, out, Ho, Wo, suppress_max);
+    else
+        hipLaunchKernelGGL(resize_planes_non_overlap_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, in, n_planes, H, W, out, Ho, Wo, suppress_max);
+    return nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------ elementwise
 // out[row][c] = x[row][c] + alpha * g[c] * y[row][c]   (g may be NULL = 1; x may be NULL = 0)
 __global__ __launch_bounds__(256) void axpy_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ g, float alpha,

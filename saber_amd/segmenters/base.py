@@ -125,6 +125,7 @@ class saber3D(saber2D):
         self.filter_threshold = 0.5
         self.batch_objects = False          # True: the tracked objects of a frame share one batched memory attention (SAM2Adapter.segment_volume(batch_objects=True)); same result
         self.device_volumes = False         # True: propagated label volumes stay on self.device (utils/labelvol.py, csrc/labelvol.hip); the segmenters' merges run there
+        self.non_overlap_masks = False      # True: a voxel that several tracked objects claim goes to the one with the highest logit, not the last painted (SAM2Adapter.segment_volume(non_overlap_masks=True))
 
     def propagate(self, mask_shape, target_class: Optional[int] = 1):
         """Seed masks into the adapter and propagate bidirectionally (reference :265-280).  With device_volumes the volume comes back
@@ -133,6 +134,8 @@ class saber3D(saber2D):
         route = {"device_volume": True} if self.device_volumes else {}
         if self.batch_objects:
             route["batch_objects"] = True
+        if self.non_overlap_masks:
+            route["non_overlap_masks"] = True
         vol = self.video_predictor.segment_volume(start_frame_idx=self.ann_frame_idx, masks=arrays, vol_shape=mask_shape,
                                                   max_frame_num_to_track=self.nframes, min_presence_score=self.filter_threshold, **route)
         self.video_predictor.reset_state()
