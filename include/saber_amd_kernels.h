@@ -135,6 +135,27 @@ int saber_k_fill_holes(const float* in, int n_planes, int H, int W, int max_area
 int saber_k_mask_small_regions(const uint32_t* bits_in, int n, int H, int W, int min_area, uint32_t* bits_out, int32_t* changed, int32_t* area,
                                int32_t* box_xyxy, void* workspace, size_t workspace_bytes, void* stream);
 size_t saber_k_mask_small_regions_bytes(int H, int W);
+/* Run-length form of bit-packed masks (csrc/rle.hip): upstream's uncompressed RLE, what SAM2AutomaticMaskGenerator returns with
+ * output_mode="uncompressed_rle".  A mask is flattened in column-major order (pixel (y, x) has position x H + y); its `counts` alternate runs
+ * of zeros and ones, start with a zeros run (0 when pixel (0,0) is set) and sum to H W.  bits: (n,H,W32) uint32 rows, W32 = ceil(W / 32), bit b
+ * of word w of a row = pixel 32w+b; bits at x >= W are not pixels: ignored on input, zero on output.  H W < 2^31; counts are uint32.
+ *   saber_k_rle_count    offsets[0 .. n] <- the exclusive sum of the masks' numbers of entries (offsets[n] = the total), 64-bit, on the device.
+ *                        Three launches.  It leaves per-column ranks in `ws` for the encode.
+ *   saber_k_rle_encode   counts[offsets[i] .. offsets[i + 1]) <- the entries of mask i.  `ws` must be what saber_k_rle_count left for the same
+ *                        stack, `offsets` its output; capacity = entries `counts` holds.  One launch, no atomics: two calls give identical
+ *                        bytes.  The capacity check reads offsets[n] back (8 bytes, one wait on `stream`); no entry is written beyond a
+ *                        mask's range or the capacity whatever `ws` holds.
+ *   saber_k_rle_decode   bits_out (n,H,W32) <- the masks of the runs counts[offsets[i] .. offsets[i + 1]).  Runs are clamped at H W and pixels
+ *                        behind the last run are zero, so malformed counts never write outside bits_out.  A memset and two launches.
+ * workspace: device memory of the caller, 16-byte aligned, saber_k_rle_workspace_bytes(n, H, W) bytes (8 bytes per mask column; 0 for a shape
+ * that is an error).  A null pointer, n, H or W below 1, H W >= 2^31, a workspace below that size (the message names it) or a capacity below
+ * offsets[n] is an error (-1, saber_k_last_error starts with "rle_count:", "rle_encode:" or "rle_decode:") and nothing is written.  No
+ * allocation inside; apart from the encode's capacity check no synchronisation. */
+size_t saber_k_rle_workspace_bytes(int n, int H, int W);
+int saber_k_rle_count(const uint32_t* bits, int n, int H, int W, int64_t* offsets, void* ws, size_t ws_bytes, void* stream);
+int saber_k_rle_encode(const uint32_t* bits, int n, int H, int W, const int64_t* offsets, uint32_t* counts, int64_t capacity, void* ws, size_t ws_bytes,
+                       void* stream);
+int saber_k_rle_decode(const uint32_t* counts, const int64_t* offsets, int n, int H, int W, uint32_t* bits_out, void* stream);
 /* depth-wise Conv2d(k7, p3) of the memory fuser's ConvNeXt blocks; w (C,1,7,7) */
 int saber_k_dwconv7(const float* in, int H, int W, int C, const float* w, const float* b, float* out, void* stream);
 /* the video predictor's mask_downsample: Conv2d(1, 1, k4, s4) */

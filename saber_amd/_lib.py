@@ -151,6 +151,10 @@ SIGNATURES = {
     "saber_k_fill_holes": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, C.c_size_t, _vp]),
     "saber_k_mask_small_regions": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "saber_k_mask_small_regions_bytes": (C.c_size_t, [_i, _i]),
+    "saber_k_rle_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "saber_k_rle_count": (_i, [_vp, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
+    "saber_k_rle_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, C.c_int64, _vp, C.c_size_t, _vp]),
+    "saber_k_rle_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "saber_k_unpack_masks": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "saber_k_dwconv7": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_dwconv7_t": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

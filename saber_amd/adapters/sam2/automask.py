@@ -76,12 +76,24 @@ def get_default() -> Dict[str, Any]:
 class EngineMaskGenerator:
     """generate(image) with the contract of sam2.SAM2AutomaticMaskGenerator.generate."""
 
-    def __init__(self, engine, amg_params: Dict[str, Any], max_masks: int = 2048, min_mask_region_area: int = 0):
+    def __init__(self, engine, amg_params: Dict[str, Any], max_masks: int = 2048, min_mask_region_area: int = 0, output_mode: str = "binary_mask"):
         """min_mask_region_area: upstream's option of that name (postprocess_small_regions: holes and islands below that many pixels,
-        then a box NMS that prefers untouched masks), on the device; 0 = off: no launch, nothing allocated."""
+        then a box NMS that prefers untouched masks), on the device; 0 = off: no launch, nothing allocated.
+        output_mode: upstream's option of that name - what generate() puts under "segmentation": "binary_mask" (default) the (H,W) bool
+        array, "uncompressed_rle" the {"size", "counts"} dict encoded on the device (Engine.rle_encode; no bool array is made),
+        "coco_rle" that dict compressed by pycocotools (ImportError here when it is not installed, as upstream)."""
         from saber_amd.engine import make_amg_params
+        from saber_amd.adapters.sam2.rle import OUTPUT_MODES
         if min_mask_region_area < 0:
             raise ValueError("min_mask_region_area must be non-negative")
+        if output_mode not in OUTPUT_MODES:
+            raise ValueError(f"output_mode must be one of {list(OUTPUT_MODES)}, got {output_mode!r}")
+        if output_mode == "coco_rle":
+            try:
+                import pycocotools  # noqa: F401
+            except ImportError as e:
+                raise ImportError("output_mode 'coco_rle' needs pycocotools, which is not installed; use 'uncompressed_rle'") from e
+        self.output_mode = output_mode
         self.engine = engine
         self.params = make_amg_params(amg_params)
         self.max_masks = max_masks
@@ -101,7 +113,10 @@ class EngineMaskGenerator:
         from saber_amd.segmenters.utils import DEVICE_ROW_KEY, DeviceMaskRows
         H, W = image.shape[:2]
         bits, meta = self.generate_device(image)
-        masks = unpack_bits(bits, W) if len(meta) else []
+        if self.output_mode != "binary_mask":
+            masks = self._rle_segmentations(bits, len(meta), H, W)
+        else:
+            masks = unpack_bits(bits, W) if len(meta) else []
         rows = DeviceMaskRows(self.engine, bits, H, W)
         return [{"segmentation": masks[i], DEVICE_ROW_KEY: (rows, i), "area": int(m.area), "bbox": [float(v) for v in m.bbox_xywh],
                  "predicted_iou": float(m.predicted_iou), "point_coords": [[float(m.point_xy[0]), float(m.point_xy[1])]],
@@ -109,11 +124,26 @@ class EngineMaskGenerator:
                 for i, m in enumerate(meta)]
 
 
-def build_amg(amg_params: Dict[str, Any], min_mask_area: int, device="cuda", checkpoint: Optional[str] = None, min_mask_region_area: int = 0):
+    def _rle_segmentations(self, bits, n: int, H: int, W: int):
+        """the RLE modes' `segmentation` values: encoded on the device, one download of a few KiB per mask"""
+        from saber_amd.adapters.sam2 import rle
+        if n == 0:
+            return []
+        counts, offsets = self.engine.rle_encode(bits, W)
+        out = rle.rle_dicts(counts, offsets, H, W)
+        return [rle.coco_encode_rle(r) for r in out] if self.output_mode == "coco_rle" else out
+
+
+def build_amg(amg_params: Dict[str, Any], min_mask_area: int, device="cuda", checkpoint: Optional[str] = None, min_mask_region_area: int = 0,
+              output_mode: str = "binary_mask"):
+    from saber_amd.adapters.sam2.rle import OUTPUT_MODES
     if min_mask_region_area < 0:
         raise ValueError("min_mask_region_area must be non-negative")
+    if output_mode not in OUTPUT_MODES:
+        raise ValueError(f"output_mode must be one of {list(OUTPUT_MODES)}, got {output_mode!r}")
     engine = get_engine(amg_params["sam2_cfg"], device, checkpoint)
-    return fmask.FilteredSAM2MaskGenerator(base_generator=EngineMaskGenerator(engine, amg_params, min_mask_region_area=min_mask_region_area),
+    return fmask.FilteredSAM2MaskGenerator(base_generator=EngineMaskGenerator(engine, amg_params, min_mask_region_area=min_mask_region_area,
+                                                                              output_mode=output_mode),
                                            min_area_filter=min_mask_area)
 
 

@@ -382,6 +382,18 @@ extern "C" int saber_k_mask_small_regions(const uint32_t* bits_in, int n, int H,
     return kcheck(launch_small_regions(bits_in, n, H, W, min_area, bits_out, changed, area, box_xyxy, workspace, workspace_bytes, (hipStream_t)stream));
 }
 extern "C" size_t saber_k_mask_small_regions_bytes(int H, int W) { return small_regions_bytes_per_mask(H, W); }
+// run lengths of bit-packed masks, upstream's uncompressed RLE (rle.hip)
+extern "C" size_t saber_k_rle_workspace_bytes(int n, int H, int W) { return rle_workspace_bytes(n, H, W); }
+extern "C" int saber_k_rle_count(const uint32_t* bits, int n, int H, int W, int64_t* offsets, void* ws, size_t ws_bytes, void* stream) {
+    return kcheck(launch_rle_count(bits, n, H, W, offsets, ws, ws_bytes, (hipStream_t)stream));
+}
+extern "C" int saber_k_rle_encode(const uint32_t* bits, int n, int H, int W, const int64_t* offsets, uint32_t* counts, int64_t capacity, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    return kcheck(launch_rle_encode(bits, n, H, W, offsets, counts, capacity, ws, ws_bytes, (hipStream_t)stream));
+}
+extern "C" int saber_k_rle_decode(const uint32_t* counts, const int64_t* offsets, int n, int H, int W, uint32_t* bits_out, void* stream) {
+    return kcheck(launch_rle_decode(counts, offsets, n, H, W, bits_out, (hipStream_t)stream));
+}
 extern "C" int saber_k_add_to_bf16(const float* x, const float* y, int y_rows, uint16_t* out_bf16, float* out_f32, int64_t rows, int C, void* stream) {
     return kcheck(launch_add_to_bf16(x, y, y_rows, out_bf16, out_f32, rows, C, (hipStream_t)stream));
 }

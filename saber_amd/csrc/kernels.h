@@ -115,6 +115,15 @@ void ccl8_merge_planes(uint32_t* lab, int H, int W, int64_t n, unsigned blocks, 
 size_t small_regions_bytes_per_mask(int H, int W);
 const char* launch_small_regions(const uint32_t* in, int n, int H, int W, int min_area, uint32_t* out, int32_t* changed, int32_t* area, int32_t* box_xyxy,
                                  void* workspace, size_t workspace_bytes, hipStream_t s);
+// ------------------------------------------------------------------ rle.hip: column-major run lengths (upstream's uncompressed RLE) of bit-packed masks
+// bits: (n,H,W32) uint32 rows.  count: offsets[n + 1] <- exclusive sum of the masks' numbers of entries, and the per-column ranks the encode
+// needs, in ws (rle_workspace_bytes(n, H, W), 16-byte aligned); encode: the entries at their offsets - with the ws count left, and one 8-byte
+// read of offsets[n] on the host for the capacity check; decode: bits_out <- the masks of the runs, clamped at H W, zero padding
+size_t rle_workspace_bytes(int n, int H, int W);
+const char* launch_rle_count(const uint32_t* bits, int n, int H, int W, int64_t* offsets, void* ws, size_t ws_bytes, hipStream_t s);
+const char* launch_rle_encode(const uint32_t* bits, int n, int H, int W, const int64_t* offsets, uint32_t* counts, int64_t capacity, void* ws, size_t ws_bytes,
+                              hipStream_t s);
+const char* launch_rle_decode(const uint32_t* counts, const int64_t* offsets, int n, int H, int W, uint32_t* bits_out, hipStream_t s);
 const char* launch_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res,
                                     hipStream_t s);
 const char* launch_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images,

@@ -293,6 +293,57 @@ class Engine:
                                                                  C.byref(cnt), _stream()))
         return out[:cnt.value], [rec[i] for i in range(cnt.value)]
 
+    # ------------------------------------------------------------------ run-length output (csrc/rle.hip)
+    def rle_encode(self, bits: torch.Tensor, W: int):
+        """Upstream's uncompressed RLE of every mask of a bit-packed (n,H,W32) int32 device stack (include/saber_amd_kernels.h:
+        saber_k_rle_count, saber_k_rle_encode): column-major runs, zeros first.  Returns device tensors (counts int32 (total,), offsets int64
+        (n + 1,)): mask i owns counts[offsets[i]:offsets[i + 1]].  `offsets` is read back once to size `counts`: the call's one host wait
+        (the encode's capacity check re-reads its last entry on the then idle stream)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("saber_amd.Engine.rle_encode needs a ROCm device; there is no CPU fallback")
+        bits = self._check_packed("rle_encode", bits, W)
+        n, H, W = int(bits.shape[0]), int(bits.shape[1]), int(W)
+        if H * W >= 2 ** 31:
+            raise ValueError(f"rle_encode: masks of 2^31 pixels or more are not supported, got {H} x {W}")
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=self.device)
+        if n == 0 or H == 0:
+            return torch.empty((0,), dtype=torch.int32, device=self.device), offsets
+        ws = torch.empty((int(self.lib.saber_k_rle_workspace_bytes(n, H, W)),), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            if self.lib.saber_k_rle_count(_ptr(bits), n, H, W, _ptr(offsets), _ptr(ws), ws.numel(), _stream()) != 0:
+                raise ValueError(f"saber_amd: {self.lib.saber_k_last_error().decode()}")
+            total = int(offsets[n].item())                     # the host wait
+            counts = torch.empty((total,), dtype=torch.int32, device=self.device)
+            if self.lib.saber_k_rle_encode(_ptr(bits), n, H, W, _ptr(offsets), _ptr(counts), total, _ptr(ws), ws.numel(), _stream()) != 0:
+                raise ValueError(f"saber_amd: {self.lib.saber_k_last_error().decode()}")
+        return counts, offsets
+
+    def rle_decode(self, counts: torch.Tensor, offsets: torch.Tensor, H: int, W: int) -> torch.Tensor:
+        """The bit-packed (n,H,W32) int32 device stack of n masks given as uncompressed RLE (include/saber_amd_kernels.h: saber_k_rle_decode).
+        counts: int32 / uint32 device tensor, offsets: int64 (n + 1,) device tensor, ascending, offsets[n] <= len(counts).  Runs are clamped at
+        H W; padding bits are zero.  No host synchronisation."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("saber_amd.Engine.rle_decode needs a ROCm device; there is no CPU fallback")
+        for name, t, dtypes in (("counts", counts, (torch.int32, torch.uint32)), ("offsets", offsets, (torch.int64,))):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dtypes or t.dim() != 1:
+                raise ValueError(f"rle_decode: {name} must be a 1-D device tensor of {' / '.join(str(d) for d in dtypes)}")
+            if t.device != self.device:
+                raise ValueError(f"rle_decode: {name} is on {t.device}, the engine on {self.device}")
+        H, W = int(H), int(W)
+        if H < 1 or W < 1 or H * W >= 2 ** 31 or offsets.numel() < 1:
+            raise ValueError(f"rle_decode: H and W of at least 1 with H W < 2^31 and n + 1 offsets are needed, got {H} x {W}, {offsets.numel()} offsets")
+        counts, offsets = counts.contiguous(), offsets.contiguous()
+        n = int(offsets.numel()) - 1
+        bits = torch.empty((n, H, (W + 31) // 32), dtype=torch.int32, device=self.device)
+        if n == 0:
+            return bits
+        if counts.numel() == 0:
+            raise ValueError("rle_decode: every mask has at least one entry, got no counts")
+        with torch.cuda.device(self.device):
+            if self.lib.saber_k_rle_decode(_ptr(counts), _ptr(offsets), n, H, W, _ptr(bits), _stream()) != 0:
+                raise ValueError(f"saber_amd: {self.lib.saber_k_last_error().decode()}")
+        return bits
+
     def label_plane(self, bits: torch.Tensor, order: Sequence[int], H: int, W: int) -> torch.Tensor:
         plane = torch.empty((H, W), dtype=torch.uint16, device=self.device)
         n = len(order)
