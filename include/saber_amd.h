@@ -260,6 +260,15 @@ int saber_engine_set_device_amg(saber_engine* e, int enable);
  * (upstream automatic_mask_generator._process_batch), so its masks are neither upscaled nor read.  saber_amg_last_pruning: how many of the
  * last saber_amg_generate call's m2m candidates were skipped. */
 int saber_engine_set_iou_pruning(saber_engine* e, int enable);
+/* The predictor half of upstream's min_mask_region_area (off by default; callable at any time after create; 0 / 0 restores the default):
+ * SAM2AutomaticMaskGenerator(min_mask_region_area=A) builds SAM2ImagePredictor(max_hole_area=A, max_sprinkle_area=A), whose every prediction
+ * cleans its 256 x 256 logits BEFORE they are resized, thresholded and scored (saber_k_clean_lowres in include/saber_amd_kernels.h has the
+ * semantics).  With either area > 0, saber_amg_generate cleans - with params->mask_threshold - the planes its full-resolution masks are made
+ * from, for the candidates that pass the predicted-IoU filter: the planes of the m2m pass with use_m2m (the first-pass planes feed the mask
+ * prompt untouched), the first-pass planes without.  One launch per group of crops, outside the captured decode sequences; stability scores,
+ * boxes and every later filter see the cleaned planes.  Areas 0..65535.  saber_decode_points / saber_decode_prompts and the video path are not
+ * affected: they return upstream's uncleaned low-resolution logits. */
+int saber_engine_set_lowres_cleanup(saber_engine* e, int max_hole_area, int max_sprinkle_area);
 /* Prompts of 2..9 points (saber_decode_prompts) on the handle's 16-bit kernels (off by default; callable at any time after create): every
  * prompt carries 16 decoder token rows, rows 7 + points .. 15 are padding that no attention sees, and a call is run in chunks of
  * max_prompts / 2 prompts in the workspaces of max_prompts 8-token prompts (no extra memory).  0: such prompts need the EXACT precision mode

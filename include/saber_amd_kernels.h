@@ -135,6 +135,23 @@ int saber_k_fill_holes(const float* in, int n_planes, int H, int W, int max_area
 int saber_k_mask_small_regions(const uint32_t* bits_in, int n, int H, int W, int min_area, uint32_t* bits_out, int32_t* changed, int32_t* area,
                                int32_t* box_xyxy, void* workspace, size_t workspace_bytes, void* stream);
 size_t saber_k_mask_small_regions_bytes(int H, int W);
+/* Clean-up of low-resolution mask logits, in place (csrc/lowres_cleanup.hip): upstream's SAM2Transforms.postprocess_masks, which
+ * SAM2ImagePredictor(max_hole_area=h, max_sprinkle_area=s) applies to the 256 x 256 logits of every prediction before they are resized and
+ * thresholded (SAM2AutomaticMaskGenerator(min_mask_region_area=A) builds its predictor with h = s = A).  Plane k of the call is the row-major
+ * H x W plane at planes + (idx ? idx[k] : k) * H * W; with pass given, a plane whose pass[k] == 0 is skipped; idx and pass may be null,
+ * each on its own.  No two k may name the same plane.  Per plane, on its ORIGINAL values, with t = thr:
+ *   background is x <= t, foreground is x > t (IEEE: -0.0 is background at t = 0; a NaN is in neither set, joins nothing, never changes);
+ *   components are 8-connected, per polarity; rows never wrap and planes never touch; no component is exempt at the border;
+ *   max_hole_area > 0: every pixel of a background component of AT MOST max_hole_area pixels becomes (float)((double)t + 10.0);
+ *   max_sprinkle_area > 0: every pixel of a foreground component of AT MOST max_sprinkle_area pixels becomes (float)((double)t - 10.0);
+ *   every other pixel keeps its bits (only changed pixels are stored).  Both labellings are independent: a small hole inside a small
+ *   sprinkle ends at t + 10 inside an island at t - 10.
+ * 1 <= H * W <= 65536 (a plane's union-find lives in one workgroup's LDS: no workspace, whatever n is), 0 <= areas <= 65535.  Null planes,
+ * n < 0, a shape or an area out of range: -1 with a "clean_lowres:" message (saber_k_last_error), nothing is launched.  n == 0 or both areas
+ * 0: 0 without a launch.  Otherwise ONE launch of n workgroups on `stream`; no synchronisation, no allocation; two calls on equal input give
+ * equal bytes. */
+int saber_k_clean_lowres(float* planes, const int* idx, const uint8_t* pass, int n, int H, int W, float thr, int max_hole_area, int max_sprinkle_area,
+                         void* stream);
 /* Run-length form of bit-packed masks (csrc/rle.hip): upstream's uncompressed RLE, what SAM2AutomaticMaskGenerator returns with
  * output_mode="uncompressed_rle".  A mask is flattened in column-major order (pixel (y, x) has position x H + y); its `counts` alternate runs
  * of zeros and ones, start with a zeros run (0 when pixel (0,0) is set) and sum to H W.  bits: (n,H,W32) uint32 rows, W32 = ceil(W / 32), bit b

@@ -80,6 +80,7 @@ SIGNATURES = {
     "saber_amg_postprocess_small_regions": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(MaskMeta), _i, _f, _vp, C.POINTER(_i), _vp]),
     "saber_amg_last_syncs": (_i, [_vp]),
     "saber_engine_set_iou_pruning": (_i, [_vp, _i]),
+    "saber_engine_set_lowres_cleanup": (_i, [_vp, _i, _i]),
     "saber_engine_set_multipoint": (_i, [_vp, _i]),
     "saber_engine_set_device_amg": (_i, [_vp, _i]),
     "saber_amg_last_pruning": (_i, [_vp, _vp, _vp]),
@@ -151,6 +152,7 @@ SIGNATURES = {
     "saber_k_fill_holes": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, C.c_size_t, _vp]),
     "saber_k_mask_small_regions": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "saber_k_mask_small_regions_bytes": (C.c_size_t, [_i, _i]),
+    "saber_k_clean_lowres": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp]),
     "saber_k_rle_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "saber_k_rle_count": (_i, [_vp, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
     "saber_k_rle_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, C.c_int64, _vp, C.c_size_t, _vp]),

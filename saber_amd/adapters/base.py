@@ -33,6 +33,12 @@ class SAM2AdapterConfig(BaseModel):
     # mask generator: upstream's min_mask_region_area (postprocess_small_regions: holes and islands below that many pixels leave every
     # final mask, then a box NMS that prefers untouched masks), on the device.  None -> SABER_AMD_MIN_MASK_REGION_AREA, else 0 (off)
     min_mask_region_area: Optional[int] = None
+    # mask generator: the predictor half of that upstream option (SAM2ImagePredictor(max_hole_area=A, max_sprinkle_area=A), which upstream's
+    # generator builds for min_mask_region_area=A): background / foreground components of at most this many pixels of the 256 x 256 logits
+    # are filled / removed before the masks are resized, thresholded and scored.  None -> SABER_AMD_MAX_HOLE_AREA / SABER_AMD_MAX_SPRINKLE_AREA,
+    # else 0 (off); 0..65535.  An upstream build with its extension = all three options at A
+    max_hole_area: Optional[int] = None
+    max_sprinkle_area: Optional[int] = None
     light_modality: bool = False
     amg_cfg: Optional[Any] = None      # cfgAMG instance; None -> cfgAMG() defaults
     min_mask_area: int = 50
@@ -59,6 +65,13 @@ class SAM2AdapterConfig(BaseModel):
     def _check_min_mask_region_area(cls, v):
         if v is not None and v < 0:
             raise ValueError("min_mask_region_area must be non-negative")
+        return v
+
+    @field_validator("max_hole_area", "max_sprinkle_area")
+    @classmethod
+    def _check_cleanup_area(cls, v, info):
+        if v is not None and not 0 <= v <= 65535:
+            raise ValueError(f"{info.field_name} must be from 0 to 65535")
         return v
 
     @field_validator("frame_store_gb")

@@ -76,16 +76,22 @@ def get_default() -> Dict[str, Any]:
 class EngineMaskGenerator:
     """generate(image) with the contract of sam2.SAM2AutomaticMaskGenerator.generate."""
 
-    def __init__(self, engine, amg_params: Dict[str, Any], max_masks: int = 2048, min_mask_region_area: int = 0, output_mode: str = "binary_mask"):
+    def __init__(self, engine, amg_params: Dict[str, Any], max_masks: int = 2048, min_mask_region_area: int = 0, output_mode: str = "binary_mask",
+                 max_hole_area: int = 0, max_sprinkle_area: int = 0):
         """min_mask_region_area: upstream's option of that name (postprocess_small_regions: holes and islands below that many pixels,
-        then a box NMS that prefers untouched masks), on the device; 0 = off: no launch, nothing allocated.
+        then a box NMS that prefers untouched masks), on the device; 0 = off: no launch, nothing allocated.  Here it is that final-mask step
+        alone.
+        max_hole_area / max_sprinkle_area: the predictor half of that upstream option (Engine.set_lowres_cleanup: the low-res logits are
+        cleaned before they are resized, thresholded and scored); 0 = off.  Upstream's generator, built with its connected-components
+        extension, equals min_mask_region_area=A, max_hole_area=A, max_sprinkle_area=A.
         output_mode: upstream's option of that name - what generate() puts under "segmentation": "binary_mask" (default) the (H,W) bool
         array, "uncompressed_rle" the {"size", "counts"} dict encoded on the device (Engine.rle_encode; no bool array is made),
         "coco_rle" that dict compressed by pycocotools (ImportError here when it is not installed, as upstream)."""
-        from saber_amd.engine import make_amg_params
+        from saber_amd.engine import make_amg_params, _check_cleanup_areas
         from saber_amd.adapters.sam2.rle import OUTPUT_MODES
         if min_mask_region_area < 0:
             raise ValueError("min_mask_region_area must be non-negative")
+        _check_cleanup_areas("EngineMaskGenerator", max_hole_area, max_sprinkle_area)
         if output_mode not in OUTPUT_MODES:
             raise ValueError(f"output_mode must be one of {list(OUTPUT_MODES)}, got {output_mode!r}")
         if output_mode == "coco_rle":
@@ -98,15 +104,23 @@ class EngineMaskGenerator:
         self.params = make_amg_params(amg_params)
         self.max_masks = max_masks
         self.min_mask_region_area = int(min_mask_region_area)
+        self.max_hole_area, self.max_sprinkle_area = int(max_hole_area), int(max_sprinkle_area)
+
+    def cleanup_keywords(self) -> Dict[str, int]:
+        """the Engine.amg_generate keywords of the options that are on (none of them: the call of a generator without the options)"""
+        kw = {}
+        if self.min_mask_region_area > 0:
+            kw["min_mask_region_area"] = self.min_mask_region_area
+        if self.max_hole_area > 0 or self.max_sprinkle_area > 0:
+            kw.update(max_hole_area=self.max_hole_area, max_sprinkle_area=self.max_sprinkle_area)
+        return kw
 
     @torch.inference_mode()
     def generate_device(self, image):
         """image: (H,W)/(H,W,3) float32 in [0,1], numpy or device tensor -> (bits, meta) on the device."""
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(self.engine.device)
-        if self.min_mask_region_area > 0:
-            return self.engine.amg_generate(image.contiguous(), self.params, max_masks=self.max_masks, min_mask_region_area=self.min_mask_region_area)
-        return self.engine.amg_generate(image.contiguous(), self.params, max_masks=self.max_masks)
+        return self.engine.amg_generate(image.contiguous(), self.params, max_masks=self.max_masks, **self.cleanup_keywords())
 
     def generate(self, image) -> List[Dict[str, Any]]:
         from saber_amd.engine import unpack_bits
@@ -135,15 +149,18 @@ class EngineMaskGenerator:
 
 
 def build_amg(amg_params: Dict[str, Any], min_mask_area: int, device="cuda", checkpoint: Optional[str] = None, min_mask_region_area: int = 0,
-              output_mode: str = "binary_mask"):
+              output_mode: str = "binary_mask", max_hole_area: int = 0, max_sprinkle_area: int = 0):
+    from saber_amd.engine import _check_cleanup_areas
     from saber_amd.adapters.sam2.rle import OUTPUT_MODES
     if min_mask_region_area < 0:
         raise ValueError("min_mask_region_area must be non-negative")
+    _check_cleanup_areas("build_amg", max_hole_area, max_sprinkle_area)
     if output_mode not in OUTPUT_MODES:
         raise ValueError(f"output_mode must be one of {list(OUTPUT_MODES)}, got {output_mode!r}")
     engine = get_engine(amg_params["sam2_cfg"], device, checkpoint)
     return fmask.FilteredSAM2MaskGenerator(base_generator=EngineMaskGenerator(engine, amg_params, min_mask_region_area=min_mask_region_area,
-                                                                              output_mode=output_mode),
+                                                                              output_mode=output_mode, max_hole_area=max_hole_area,
+                                                                              max_sprinkle_area=max_sprinkle_area),
                                            min_area_filter=min_mask_area)
 
 

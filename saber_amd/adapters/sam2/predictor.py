@@ -37,8 +37,16 @@ class SAM2Adapter(BaseAdapter):
             else:
                 amg = cfgAMG(sam2_cfg=self._config.cfg).dict()
             self._mask_generator = build_amg(amg, self._config.min_mask_area, device=self.device, checkpoint=self._config.checkpoint,
-                                             min_mask_region_area=self._min_mask_region_area())
+                                             min_mask_region_area=self._min_mask_region_area(), **self._lowres_cleanup())
         return self._mask_generator
+
+    def _lowres_cleanup(self) -> Dict[str, int]:
+        """config.max_hole_area / max_sprinkle_area, else the environment's SABER_AMD_MAX_HOLE_AREA / SABER_AMD_MAX_SPRINKLE_AREA, else 0 (off)"""
+        from saber_amd.engine import lowres_cleanup_env_defaults
+        cfg = (self._config.max_hole_area, self._config.max_sprinkle_area)
+        env = lowres_cleanup_env_defaults() if None in cfg else (0, 0)
+        h, s = (int(c) if c is not None else e for c, e in zip(cfg, env))
+        return {"max_hole_area": h, "max_sprinkle_area": s}
 
     def _min_mask_region_area(self) -> int:
         """config.min_mask_region_area, else the environment's SABER_AMD_MIN_MASK_REGION_AREA, else 0 (off, upstream's default)"""

@@ -103,6 +103,7 @@ extern "C" int saber_amg_generate(saber_engine* e, const float* img_dev, int H, 
     const int W32 = (W + 31) >> 5;
     const size_t mask_words = (size_t)H * W32;
     const int M = prm->multimask_output ? 3 : 1;
+    const bool lowres_clean = e->lowres_hole_area > 0 || e->lowres_sprinkle_area > 0;
 
     std::vector<std::array<int, 4>> crops;
     std::vector<int> layers;
@@ -308,6 +309,11 @@ extern "C" int saber_amg_generate(saber_engine* e, const float* img_dev, int H, 
             for (const Grp& gr : groups) {
                 ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_amg_plane(iou_all + gr.k0, gr.plane_mode == 2 ? e->amg_sel + gr.k0 : nullptr, gr.G * gr.nm, gr.plane_mode, prm->pred_iou_thresh,
                                                                   e->amg_idx + gr.k0, e->amg_pass + gr.k0, s));
+                // upstream's predictor cleans the low-res logits before they are resized and scored (saber_engine_set_lowres_cleanup): the planes
+                // K8 is about to read, in place, for the candidates the IoU filter passed
+                if (lowres_clean)
+                    ENG_KP(e, PC_MASK_POST, 0.0, 0.0, launch_clean_lowres(const_cast<float*>(gr.masks), e->amg_idx + gr.k0, e->amg_pass + gr.k0, gr.G * gr.nm, 256, 256, prm->mask_threshold,
+                                                                         e->lowres_hole_area, e->lowres_sprinkle_area, s));
                 for (int g = 0; g < gr.G; ++g) {
                     const auto& box = crops[c0 + gr.ci + g];
                     DevCrop dc{{box[0], box[1], box[2], box[3]}, (int)(gr.k0 + (size_t)g * gr.nm), gr.nm, (int)(gr.pt0 + (size_t)g * gr.np), M};
@@ -361,6 +367,12 @@ extern "C" int saber_amg_generate(saber_engine* e, const float* img_dev, int H, 
         ENG_HIP(e, hipMemcpyAsync(e->amg_idx, h_plane.data(), sizeof(int) * ns_all, hipMemcpyHostToDevice, s));
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             const Grp& gr = groups[gi];
+            if (lowres_clean) {      // the survivors' planes of the group (its crops' ranges are adjacent in the list), as on the device route
+                int cnt = 0;
+                for (const CropRange& r : ranges[gi]) cnt += r.count;
+                ENG_KP(e, PC_MASK_POST, 0.0, 0.0, launch_clean_lowres(const_cast<float*>(gr.masks), e->amg_idx + ranges[gi][0].first, nullptr, cnt, 256, 256, prm->mask_threshold,
+                                                                     e->lowres_hole_area, e->lowres_sprinkle_area, s));
+            }
             for (int g = 0; g < gr.G; ++g) {
                 const CropRange& r = ranges[gi][g];
                 if (r.count == 0) continue;

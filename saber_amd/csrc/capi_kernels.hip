@@ -382,6 +382,11 @@ extern "C" int saber_k_mask_small_regions(const uint32_t* bits_in, int n, int H,
     return kcheck(launch_small_regions(bits_in, n, H, W, min_area, bits_out, changed, area, box_xyxy, workspace, workspace_bytes, (hipStream_t)stream));
 }
 extern "C" size_t saber_k_mask_small_regions_bytes(int H, int W) { return small_regions_bytes_per_mask(H, W); }
+// small holes and sprinkles of low-resolution logit planes, in place (lowres_cleanup.hip)
+extern "C" int saber_k_clean_lowres(float* planes, const int* idx, const uint8_t* pass, int n, int H, int W, float thr, int max_hole_area, int max_sprinkle_area,
+                                    void* stream) {
+    return kcheck(launch_clean_lowres(planes, idx, pass, n, H, W, thr, max_hole_area, max_sprinkle_area, (hipStream_t)stream));
+}
 // run lengths of bit-packed masks, upstream's uncompressed RLE (rle.hip)
 extern "C" size_t saber_k_rle_workspace_bytes(int n, int H, int W) { return rle_workspace_bytes(n, H, W); }
 extern "C" int saber_k_rle_count(const uint32_t* bits, int n, int H, int W, int64_t* offsets, void* ws, size_t ws_bytes, void* stream) {

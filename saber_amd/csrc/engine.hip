@@ -160,6 +160,13 @@ extern "C" int saber_engine_set_iou_pruning(saber_engine* e, int enable) {
     if ((bool)enable != e->iou_prune) { e->iou_prune = enable != 0; eng_graphs_flush(e); }      // (captured decode sequences contain the choice)
     return SABER_OK;
 }
+extern "C" int saber_engine_set_lowres_cleanup(saber_engine* e, int max_hole_area, int max_sprinkle_area) {
+    if (!e) return SABER_ERR_INVALID;
+    if (max_hole_area < 0 || max_hole_area > 65535 || max_sprinkle_area < 0 || max_sprinkle_area > 65535)
+        return eng_fail(e, SABER_ERR_INVALID, "set_lowres_cleanup: max_hole_area and max_sprinkle_area must be 0 to 65535");
+    e->lowres_hole_area = max_hole_area; e->lowres_sprinkle_area = max_sprinkle_area;      // (outside the captured decode sequences: nothing to flush)
+    return SABER_OK;
+}
 extern "C" int saber_engine_set_multipoint(saber_engine* e, int enable) {
     if (!e) return SABER_ERR_INVALID;
     if (enable && e->max_prompts < 2) return eng_fail(e, SABER_ERR_INVALID, "set_multipoint: the 16-token route needs max_prompts >= 2 (chunks of max_prompts / 2 prompts)");

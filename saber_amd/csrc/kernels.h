@@ -115,6 +115,11 @@ void ccl8_merge_planes(uint32_t* lab, int H, int W, int64_t n, unsigned blocks, 
 size_t small_regions_bytes_per_mask(int H, int W);
 const char* launch_small_regions(const uint32_t* in, int n, int H, int W, int min_area, uint32_t* out, int32_t* changed, int32_t* area, int32_t* box_xyxy,
                                  void* workspace, size_t workspace_bytes, hipStream_t s);
+// ------------------------------------------------------------------ lowres_cleanup.hip: small holes / sprinkles of low-res logit planes, in place
+// plane k of the call is planes + (idx ? idx[k] : k) * H * W; a plane whose pass[k] == 0 is skipped (both may be null).  H W <= 65536, areas
+// 0..65535; n == 0 or both areas 0: no launch.  One launch on s, one workgroup per plane, no workspace.
+const char* launch_clean_lowres(float* planes, const int* idx, const uint8_t* pass, int n, int H, int W, float thr, int max_hole_area, int max_sprinkle_area,
+                                hipStream_t s);
 // ------------------------------------------------------------------ rle.hip: column-major run lengths (upstream's uncompressed RLE) of bit-packed masks
 // bits: (n,H,W32) uint32 rows.  count: offsets[n + 1] <- exclusive sum of the masks' numbers of entries, and the per-column ranks the encode
 // needs, in ws (rle_workspace_bytes(n, H, W), 16-byte aligned); encode: the entries at their offsets - with the ws count left, and one 8-byte

@@ -6,6 +6,7 @@ Python exceptions (ValueError for bad configuration, RuntimeError for state / HI
 that the reference's per-task accounting (saber/utils/parallelization.py:129-135) keeps working.
 """
 import ctypes as C
+import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -200,12 +201,24 @@ class Engine:
         return low, iou, obj
 
     # ------------------------------------------------------------------ AMG
-    def amg_generate(self, img: torch.Tensor, params: "_lib.AmgParams", max_masks: int = 1024, min_mask_region_area: int = 0):
+    def amg_generate(self, img: torch.Tensor, params: "_lib.AmgParams", max_masks: int = 1024, min_mask_region_area: int = 0,
+                     max_hole_area: int = 0, max_sprinkle_area: int = 0):
         """img: (H,W) or (H,W,3) float32 in [0,1].  Returns (bits uint32 (n,H,W32) device tensor, list of MaskMeta).
         min_mask_region_area > 0: upstream's option of that name - postprocess_small_regions on the final masks with the NMS threshold
-        max(params.box_nms_thresh, params.crop_nms_thresh); 0 (default) = off: no launch, nothing allocated."""
+        max(params.box_nms_thresh, params.crop_nms_thresh); 0 (default) = off: no launch, nothing allocated.
+        max_hole_area / max_sprinkle_area > 0: the predictor half of that upstream option for this call (set_lowres_cleanup; the handle's
+        own setting is back afterwards); 0 / 0 (default) = the handle's setting, which is off unless set_lowres_cleanup was called.  An
+        upstream generator built with its connected-components extension equals min_mask_region_area=A, max_hole_area=A, max_sprinkle_area=A."""
         if min_mask_region_area < 0:
             raise ValueError("min_mask_region_area must be non-negative")
+        _check_cleanup_areas("amg_generate", max_hole_area, max_sprinkle_area)
+        if max_hole_area or max_sprinkle_area:
+            keep = getattr(self, "_lowres_cleanup", (0, 0))
+            self.set_lowres_cleanup(max_hole_area, max_sprinkle_area)
+            try:
+                return self.amg_generate(img, params, max_masks=max_masks, min_mask_region_area=min_mask_region_area)
+            finally:
+                self.set_lowres_cleanup(*keep)
         if min_mask_region_area > 0:
             bits, meta = self.amg_generate(img, params, max_masks=max_masks)
             return self.postprocess_small_regions(bits, meta, img.shape[0], img.shape[1], min_mask_region_area,
@@ -234,6 +247,34 @@ class Engine:
         self._check(st)
         n = cnt.value
         return bits[:n], [meta[i] for i in range(n)]
+
+    # ------------------------------------------------------------------ low-res clean-up (csrc/lowres_cleanup.hip)
+    def clean_lowres(self, planes: torch.Tensor, max_hole_area: int, max_sprinkle_area: int, mask_threshold: float = 0.0) -> torch.Tensor:
+        """Upstream's SAM2Transforms.postprocess_masks on an (n,H,W) float32 device tensor of mask logits, IN PLACE (include/saber_amd_kernels.h:
+        saber_k_clean_lowres): per plane, 8-connected background components (x <= mask_threshold) of at most max_hole_area pixels become
+        mask_threshold + 10, foreground components of at most max_sprinkle_area pixels mask_threshold - 10, both found on the original
+        values.  H * W <= 65536, areas 0..65535 (0 = that half off).  Returns `planes`.  One launch, no host synchronisation."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("saber_amd.Engine.clean_lowres needs a ROCm device; there is no CPU fallback")
+        if not isinstance(planes, torch.Tensor) or not planes.is_cuda or planes.dtype != torch.float32 or planes.dim() != 3 or not planes.is_contiguous():
+            raise ValueError("clean_lowres: planes must be a contiguous (n,H,W) float32 device tensor")
+        if planes.device != self.device:
+            raise ValueError(f"clean_lowres: the planes are on {planes.device}, the engine on {self.device}")
+        _check_cleanup_areas("clean_lowres", max_hole_area, max_sprinkle_area)
+        n, H, W = (int(v) for v in planes.shape)
+        if n == 0:
+            return planes
+        with torch.cuda.device(self.device):
+            if self.lib.saber_k_clean_lowres(_ptr(planes), None, None, n, H, W, float(mask_threshold), int(max_hole_area), int(max_sprinkle_area), _stream()) != 0:
+                raise ValueError(f"saber_amd: {self.lib.saber_k_last_error().decode()}")
+        return planes
+
+    def set_lowres_cleanup(self, max_hole_area: int, max_sprinkle_area: int):
+        """The predictor half of upstream's min_mask_region_area in amg_generate (include/saber_amd.h: saber_engine_set_lowres_cleanup): the
+        low-res planes the masks are made from are cleaned before they are resized, thresholded and scored.  0, 0 (default) = off."""
+        _check_cleanup_areas("set_lowres_cleanup", max_hole_area, max_sprinkle_area)
+        self._check(self.lib.saber_engine_set_lowres_cleanup(self.h, int(max_hole_area), int(max_sprinkle_area)))
+        self._lowres_cleanup = (int(max_hole_area), int(max_sprinkle_area))
 
     # ------------------------------------------------------------------ small regions (csrc/smallregions.hip)
     SMALL_REGIONS_WS_BYTES = 128 << 20      # label workspace of remove_small_regions: the masks are run in passes of as many as it holds
@@ -601,6 +642,26 @@ class Engine:
 
     def encoder_flops(self) -> float:
         return float(self.lib.saber_encoder_flops(self.h))
+
+
+def _check_cleanup_areas(who: str, max_hole_area, max_sprinkle_area):
+    for name, v in (("max_hole_area", max_hole_area), ("max_sprinkle_area", max_sprinkle_area)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 65535:
+            raise ValueError(f"{who}: {name} must be an integer from 0 to 65535, got {v!r}")
+
+
+def lowres_cleanup_env_defaults():
+    """(max_hole_area, max_sprinkle_area) from SABER_AMD_MAX_HOLE_AREA / SABER_AMD_MAX_SPRINKLE_AREA; unset or empty = 0."""
+    out = []
+    for var in ("SABER_AMD_MAX_HOLE_AREA", "SABER_AMD_MAX_SPRINKLE_AREA"):
+        txt = os.environ.get(var, "").strip()
+        try:
+            v = int(txt) if txt else 0
+        except ValueError:
+            raise ValueError(f"{var} must be an integer from 0 to 65535, got {txt!r}") from None
+        _check_cleanup_areas(var, v, 0)
+        out.append(v)
+    return tuple(out)
 
 
 def unpack_bits(bits: torch.Tensor, W: int) -> np.ndarray:

@@ -145,6 +145,7 @@ class propagationSegmenter(saber3D):
         gen = self.adapter._generator()
         eng, params = gen.base_generator.engine, gen.base_generator.params
         region_area = getattr(gen.base_generator, "min_mask_region_area", 0)       # the adapter's small-region clean-up, per slice
+        hole_area, sprinkle_area = getattr(gen.base_generator, "max_hole_area", 0), getattr(gen.base_generator, "max_sprinkle_area", 0)
         engines = [eng]
         if handles_per_gpu > 1:
             # replicas of the PRIMARY engine's model (the adapter's own `cfg` field may name another trunk)
@@ -167,7 +168,9 @@ class propagationSegmenter(saber3D):
                 plane, _ = segment_slice_to_plane(engine, sl, params, min_mask_area=self.min_mask_area,
                                                   remove_repeating_masks=self.remove_repeating_masks, max_masks=gen.base_generator.max_masks,
                                                   classifier=classifier, target_class=1, classifier_min_area=self.batchsize,
-                                                  **({"min_mask_region_area": region_area} if region_area > 0 else {}))
+                                                  **({"min_mask_region_area": region_area} if region_area > 0 else {}),
+                                                  **({"max_hole_area": hole_area, "max_sprinkle_area": sprinkle_area}
+                                                     if hole_area > 0 or sprinkle_area > 0 else {}))
                 return plane
             return one
 

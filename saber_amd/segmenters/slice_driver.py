@@ -63,23 +63,25 @@ def classified_paint_lut(areas, min_area: int) -> np.ndarray:
 
 def segment_slice_to_plane(engine, raw_slice: torch.Tensor, params, min_mask_area: int = 50,
                            remove_repeating_masks: bool = True, max_masks: int = 2048, classifier=None, target_class: int = 1,
-                           classifier_min_area: int = 32, min_mask_region_area: int = 0) -> Tuple[torch.Tensor, int]:
+                           classifier_min_area: int = 32, min_mask_region_area: int = 0, max_hole_area: int = 0,
+                           max_sprinkle_area: int = 0) -> Tuple[torch.Tensor, int]:
     """raw_slice: (H,W) uint16/float32 device tensor.  Returns ((H,W) uint16 label plane on device, n masks).
     max_masks is the same capacity the adapter path uses (EngineMaskGenerator.max_masks); a denser slice is retried once with the
     count the engine reports instead of failing the volume.
     classifier (a Predictor on an engine handle no other thread uses; None = no classifier filter): the slice takes the classifier
     branch of _apply_classifier for target_class > 0, with classifier_min_area as the component area filter; n masks is then the number
     of painted components.  The semantic branch (target_class <= 0) is not a slice-loop result: ValueError.
-    min_mask_region_area > 0: the generator's small-region clean-up (Engine.amg_generate) before anything reads the masks."""
+    min_mask_region_area > 0: the generator's small-region clean-up (Engine.amg_generate) before anything reads the masks.
+    max_hole_area / max_sprinkle_area > 0: the generator's clean-up of the low-res logits (Engine.amg_generate), for this call."""
     if classifier is not None and (target_class is None or target_class <= 0):
         raise ValueError(f"segment_slice_to_plane: the classifier route needs target_class > 0, got {target_class} (the semantic branch is "
                          "not part of the slice loop)")
     H, W = raw_slice.shape
     img = engine.prepare(raw_slice)
-    if min_mask_region_area > 0:
-        bits, meta = engine.amg_generate(img, params, max_masks=max_masks, min_mask_region_area=min_mask_region_area)
-    else:
-        bits, meta = engine.amg_generate(img, params, max_masks=max_masks)
+    kw = {"min_mask_region_area": min_mask_region_area} if min_mask_region_area > 0 else {}
+    if max_hole_area > 0 or max_sprinkle_area > 0:
+        kw.update(max_hole_area=max_hole_area, max_sprinkle_area=max_sprinkle_area)
+    bits, meta = engine.amg_generate(img, params, max_masks=max_masks, **kw)
     if len(meta) == 0:
         return torch.zeros((H, W), dtype=torch.uint16, device=raw_slice.device), 0
     inter = engine.pair_intersections(bits, H, W).cpu().numpy() if remove_repeating_masks else None
