@@ -70,6 +70,19 @@ int saber_k_prepare(const void* img, int dtype, int H, int W, float* out, float*
  * (area, inter, union, x0, y0, x1, y1, pad). bits: n x H x ceil(W/32). */
 int saber_k_mask_post(const float* lowres, int n, int crop_x0, int crop_y0, int crop_w, int crop_h, int H, int W, float thr,
                       float offset, uint32_t* bits, int32_t* stats, void* stream);
+/* The same with the two optional device tables of the mask generator: idx (n int32) - mask i reads plane idx[i] of lowres; pass (n bytes) -
+ * masks with 0 are skipped: their bits are left as they are and their stats are the initial record (area 0, box (1<<30, 1<<30, -1, -1)).
+ * Either pointer may be null. */
+int saber_k_mask_post_ex(const float* lowres, const int* idx, const uint8_t* pass, int n, int crop_x0, int crop_y0, int crop_w, int crop_h,
+                         int H, int W, float thr, float offset, uint32_t* bits, int32_t* stats, void* stream);
+
+/* K1a: crop -> antialiased bilinear resize to res x res (ATen's tap rule) -> ImageNet normalisation.  img fp32 (H,W) for channels 1 / -1 or
+ * (H,W,3) for channels 3; crops_dev: n x (x0, y0, x1, y1) int32 on the device; out [n][3][res][res].  channels -1: one grey plane that
+ * already carries the model's normalisation (replicated, no statistics).  res must be a positive multiple of 16. */
+int saber_k_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res, void* stream);
+/* K1b: Hiera PatchEmbed Conv2d(3->C, k7 s4 p3) of pix [n_images][3][1024][1024] + bias + pos, rows in the engine's token order:
+ * out [n_images][65536][C].  wt [tap = (c*7 + ky)*7 + kx][C], pos [65536][C] in token order.  C: 96 | 112 | 144. */
+int saber_k_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images, int C, void* stream);
 
 /* ---- SAM2 video (memory) path: the per-frame arithmetic the reference's segment_volume (saber/adapters/sam2/predictor.py:232-348) makes the
  * third-party video predictor run besides encoder and mask decoder (upstream sam2/modeling/{memory_attention,memory_encoder,sam2_base}.py).

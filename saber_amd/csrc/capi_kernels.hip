@@ -143,6 +143,24 @@ extern "C" int saber_k_mask_post(const float* lowres, int n, int crop_x0, int cr
                                    reinterpret_cast<MaskStats*>(stats), (hipStream_t)stream));
 }
 
+extern "C" int saber_k_mask_post_ex(const float* lowres, const int* idx, const uint8_t* pass, int n, int crop_x0, int crop_y0, int crop_w, int crop_h,
+                                    int H, int W, float thr, float offset, uint32_t* bits, int32_t* stats, void* stream) {
+    return kcheck(launch_mask_post(lowres, idx, n, crop_x0, crop_y0, crop_w, crop_h, H, W, thr, offset, bits,
+                                   reinterpret_cast<MaskStats*>(stats), (hipStream_t)stream, pass));
+}
+
+extern "C" int saber_k_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res, void* stream) {
+    // the launcher's grid is res / 16 blocks per axis: any other res would leave a border of `out` unwritten
+    if (res <= 0 || (res % 16) != 0) return kfail("resize_normalize: res must be a positive multiple of 16");
+    if (n <= 0) return 0;
+    return kcheck(launch_resize_normalize(img, H, W, channels, crops_dev, n, out, res, (hipStream_t)stream));
+}
+
+extern "C" int saber_k_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images, int C, void* stream) {
+    if (n_images <= 0) return 0;
+    return kcheck(launch_patch_embed(pix, wt, bias, pos, out, n_images, C, 1024, (hipStream_t)stream));
+}
+
 extern "C" int saber_k_perm_index(int y, int x, int stage) { return perm_index(y, x, stage); }
 
 extern "C" int saber_k_dec_i2t(const uint16_t* X, int64_t x_batch_stride, const uint16_t* peq, const uint16_t* Kt, const float* tk, float kscale, const float* cb,
