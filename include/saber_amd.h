@@ -281,6 +281,21 @@ int saber_amg_last_pruning(const saber_engine* e, int64_t* pruned, int64_t* m2m_
 int saber_label_plane(saber_engine* e, const uint32_t* bits_dev, const int* order_host, int n, int H, int W,
                       uint16_t* plane_dev, void* stream);
 
+/* Sliding-window masks in full-frame form (csrc/windows.hip; records and outputs: saber_amd_kernels.h, saber_k_place_window_masks /
+ * saber_k_window_label_stack).  src_dev: src_words 32-bit words on the device; table_host: n records on the HOST, checked before anything
+ * is launched: h, w >= 1; 0 <= y0, y0 + h <= H; 0 <= x0, x0 + w <= W; 0 <= src_word, src_word + h * ceil(w / 32) <= src_words; also
+ * H W < 2^31, elem_bytes in {1, 2, 4}, 0 <= first, 0 <= count, first + count <= n and first + count <= 255 (1 byte) / 65535 (2 bytes).
+ * A violation is SABER_ERR_INVALID with a message that names the record; nothing is launched and the output is untouched.  n == 0 /
+ * count == 0 succeed without a launch.  The table is uploaded on `stream`; one launch, accounted under the profile class of
+ * saber_label_plane; no host synchronisation.  The uploaded table lives in one buffer of the handle (it doubles when it is outgrown; an
+ * outgrown buffer is released with the handle), so the calls of one handle must be issued on one stream at a time, as those of
+ * saber_label_plane. */
+struct saber_window_mask;
+int saber_place_window_masks(saber_engine* e, const uint32_t* src_dev, int64_t src_words, const struct saber_window_mask* table_host, int n, int H,
+                             int W, uint32_t* out_dev, void* stream);
+int saber_window_label_stack(saber_engine* e, const uint32_t* src_dev, int64_t src_words, const struct saber_window_mask* table_host, int n, int first,
+                             int count, int H, int W, int elem_bytes, void* out_dev, void* stream);
+
 /* out_inter_dev[i*n+j] = |mask_i AND mask_j| in pixels for the n bit-packed masks: the integer counts behind
  * remove_duplicate_masks' IoU (saber/segmenters/utils.py:21-29); IoU = inter / (area_i + area_j - inter). */
 int saber_mask_pair_intersections(saber_engine* e, const uint32_t* bits_dev, int n, int H, int W, int32_t* out_inter_dev, void* stream);

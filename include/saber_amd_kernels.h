@@ -186,6 +186,28 @@ int saber_k_rle_count(const uint32_t* bits, int n, int H, int W, int64_t* offset
 int saber_k_rle_encode(const uint32_t* bits, int n, int H, int W, const int64_t* offsets, uint32_t* counts, int64_t capacity, void* ws, size_t ws_bytes,
                        void* stream);
 int saber_k_rle_decode(const uint32_t* counts, const int64_t* offsets, int n, int H, int W, uint32_t* bits_out, void* stream);
+/* Sliding-window masks (csrc/windows.hip): the masks of saber2D.segment_image(use_sliding_window=True) (saber/segmenters/base.py:103-150) are
+ * window-sized; rasterize_masks (:214-232) pastes each into a full frame and masks_to_array (saber/filters/masks.py:157-182) stacks them.
+ * A record names one window-sized bit-packed mask inside a ragged buffer `src` of 32-bit words: it occupies h * ceil(w / 32) words from
+ * src + src_word, row-major with row pitch ceil(w / 32), bit b of word k of a row = pixel x = 32k + b (the generator's layout), and its pixel
+ * (0, 0) lies at pixel (y0, x0) of the H x W frame.  Bits at x >= w of a row's last word are not pixels: they may hold anything. */
+typedef struct saber_window_mask {
+    int64_t src_word;
+    int32_t y0, x0, h, w;
+} saber_window_mask;
+/*   saber_k_place_window_masks   out (n,H,W32) uint32, W32 = ceil(W / 32): mask i in full-frame rows, zero outside its window, zero at x >= W.
+ *                                Every word of out is written exactly once (no memset, no atomics): one launch, whatever n is.
+ *   saber_k_window_label_stack   out (count,H,W) of elem_bytes = 1, 2 or 4 (unsigned): plane i holds first + i + 1 where mask first + i covers
+ *                                the pixel and 0 elsewhere - planes first .. first + count - 1 of masks_to_array's stack.  Every element is
+ *                                written exactly once: one launch.
+ * table_dev: n (place) / at least first + count (stack) records ON THE DEVICE, 8-byte aligned.  The raw entries check the call's own
+ * arguments only (a null pointer, a negative count, a shape below 1, H W >= 2^31, elem_bytes, first + count against the element's range:
+ * -1, saber_k_last_error starts with "place_window_masks:" / "window_label_stack:", nothing is launched); the records are the caller's
+ * responsibility: every window inside the frame and inside src (saber_place_window_masks / saber_window_label_stack of saber_amd.h check them
+ * on the host).  n == 0 / count == 0: 0 without a launch.  No synchronisation and no allocation inside; two calls give equal bytes. */
+int saber_k_place_window_masks(const uint32_t* src, const saber_window_mask* table_dev, int n, int H, int W, uint32_t* out, void* stream);
+int saber_k_window_label_stack(const uint32_t* src, const saber_window_mask* table_dev, int first, int count, int H, int W, int elem_bytes, void* out,
+                               void* stream);
 /* depth-wise Conv2d(k7, p3) of the memory fuser's ConvNeXt blocks; w (C,1,7,7) */
 int saber_k_dwconv7(const float* in, int H, int W, int C, const float* w, const float* b, float* out, void* stream);
 /* the video predictor's mask_downsample: Conv2d(1, 1, k4, s4) */

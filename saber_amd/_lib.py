@@ -51,6 +51,19 @@ class RefineParams(C.Structure):
                 ("keep_surface_membranes", C.c_int), ("min_roi_size", C.c_float * 3)]
 
 
+class WindowMask(C.Structure):
+    """saber_window_mask (include/saber_amd_kernels.h): one window-sized bit-packed mask inside a ragged word buffer and its place in the frame"""
+    _fields_ = [("src_word", C.c_int64), ("y0", C.c_int32), ("x0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+def window_table(records):
+    """a (WindowMask * n) array from an iterable of (src_word, y0, x0, h, w); an array of WindowMask passes through; no records give an array of length 0"""
+    if isinstance(records, C.Array) and getattr(records, "_type_", None) is WindowMask:
+        return records
+    records = [tuple(int(v) for v in r) for r in records]
+    return (WindowMask * len(records))(*records)
+
+
 class ProfileClass(C.Structure):
     _fields_ = [("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -92,6 +105,8 @@ SIGNATURES = {
     "saber_engine_graph_stats": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "saber_label_plane": (_i, [_vp, _vp, C.POINTER(_i), _i, _i, _i, _vp, _vp]),
     "saber_mask_pair_intersections": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "saber_place_window_masks": (_i, [_vp, _vp, C.c_int64, C.POINTER(WindowMask), _i, _i, _i, _vp, _vp]),
+    "saber_window_label_stack": (_i, [_vp, _vp, C.c_int64, C.POINTER(WindowMask), _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "saber_separate_masks": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
     "saber_smooth_labels": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, C.POINTER(_i), _vp]),
     "saber_gaussian_smoothing_3d": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp]),
@@ -161,6 +176,8 @@ SIGNATURES = {
     "saber_k_rle_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, C.c_int64, _vp, C.c_size_t, _vp]),
     "saber_k_rle_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "saber_k_unpack_masks": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "saber_k_place_window_masks": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "saber_k_window_label_stack": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "saber_k_dwconv7": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_dwconv7_t": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_conv3x3s2_t_batched": (_i, [_vp, C.c_int64, _i, _i, _i, _vp, _vp, _i, _vp, C.c_int64, _i, _vp]),

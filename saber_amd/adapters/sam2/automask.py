@@ -123,20 +123,28 @@ class EngineMaskGenerator:
         return self.engine.amg_generate(image.contiguous(), self.params, max_masks=self.max_masks, **self.cleanup_keywords())
 
     def generate(self, image) -> List[Dict[str, Any]]:
-        from saber_amd.engine import unpack_bits
-        from saber_amd.segmenters.utils import DEVICE_ROW_KEY, DeviceMaskRows
         H, W = image.shape[:2]
         bits, meta = self.generate_device(image)
+        return self._dicts(bits, meta, H, W)
+
+    def _dicts(self, bits, meta, H: int, W: int) -> List[Dict[str, Any]]:
+        """generate()'s list for what generate_device returned"""
+        from saber_amd.engine import unpack_bits
+        from saber_amd.segmenters.utils import DEVICE_ROW_KEY, DeviceMaskRows
         if self.output_mode != "binary_mask":
             masks = self._rle_segmentations(bits, len(meta), H, W)
         else:
             masks = unpack_bits(bits, W) if len(meta) else []
         rows = DeviceMaskRows(self.engine, bits, H, W)
-        return [{"segmentation": masks[i], DEVICE_ROW_KEY: (rows, i), "area": int(m.area), "bbox": [float(v) for v in m.bbox_xywh],
-                 "predicted_iou": float(m.predicted_iou), "point_coords": [[float(m.point_xy[0]), float(m.point_xy[1])]],
-                 "stability_score": float(m.stability_score), "crop_box": [float(v) for v in m.crop_box_xywh]}
-                for i, m in enumerate(meta)]
+        return [{"segmentation": masks[i], DEVICE_ROW_KEY: (rows, i), **rec} for i, rec in enumerate(self.records(meta))]
 
+    @staticmethod
+    def records(meta) -> List[Dict[str, Any]]:
+        """the scalar fields of generate()'s dicts, one per MaskMeta record, in its key order (no `segmentation`): what the filters behind
+        the generator read.  Shared by generate() and the device route of the sliding windows (saber_amd/segmenters/windows.py)."""
+        return [{"area": int(m.area), "bbox": [float(v) for v in m.bbox_xywh], "predicted_iou": float(m.predicted_iou),
+                 "point_coords": [[float(m.point_xy[0]), float(m.point_xy[1])]], "stability_score": float(m.stability_score),
+                 "crop_box": [float(v) for v in m.crop_box_xywh]} for m in meta]
 
     def _rle_segmentations(self, bits, n: int, H: int, W: int):
         """the RLE modes' `segmentation` values: encoded on the device, one download of a few KiB per mask"""

@@ -417,6 +417,14 @@ extern "C" int saber_k_rle_encode(const uint32_t* bits, int n, int H, int W, con
 extern "C" int saber_k_rle_decode(const uint32_t* counts, const int64_t* offsets, int n, int H, int W, uint32_t* bits_out, void* stream) {
     return kcheck(launch_rle_decode(counts, offsets, n, H, W, bits_out, (hipStream_t)stream));
 }
+// window-sized bit-packed masks -> full-frame rows / label stack (windows.hip)
+extern "C" int saber_k_place_window_masks(const uint32_t* src, const saber_window_mask* table_dev, int n, int H, int W, uint32_t* out, void* stream) {
+    return kcheck(launch_window_place(src, table_dev, n, H, W, out, (hipStream_t)stream));
+}
+extern "C" int saber_k_window_label_stack(const uint32_t* src, const saber_window_mask* table_dev, int first, int count, int H, int W, int elem_bytes, void* out,
+                                          void* stream) {
+    return kcheck(launch_window_stack(src, table_dev, first, count, H, W, elem_bytes, out, (hipStream_t)stream));
+}
 extern "C" int saber_k_add_to_bf16(const float* x, const float* y, int y_rows, uint16_t* out_bf16, float* out_f32, int64_t rows, int C, void* stream) {
     return kcheck(launch_add_to_bf16(x, y, y_rows, out_bf16, out_f32, rows, C, (hipStream_t)stream));
 }

@@ -135,6 +135,7 @@ struct saber_engine {
     uint32_t* amg_crop_bits = nullptr; size_t amg_crop_words = 0;   // one crop's pred_iou survivors
     MaskStats* amg_stats = nullptr; int* amg_idx = nullptr; size_t amg_stats_cap = 0;
     int* order_dev = nullptr; size_t order_cap = 0;
+    void* win_table_dev = nullptr; size_t win_table_cap = 0;        // windows.hip: the uploaded saber_window_mask table (records), grown on demand
 
     // hipGraph replay of the AMG driver's launch sequences (one batched encoder pass, 12 decoder batches per slice with the default
     // pyramid): a sequence is run eagerly the first time its arguments are seen, captured the second time, replayed from then on

@@ -129,6 +129,13 @@ const char* launch_rle_count(const uint32_t* bits, int n, int H, int W, int64_t*
 const char* launch_rle_encode(const uint32_t* bits, int n, int H, int W, const int64_t* offsets, uint32_t* counts, int64_t capacity, void* ws, size_t ws_bytes,
                               hipStream_t s);
 const char* launch_rle_decode(const uint32_t* counts, const int64_t* offsets, int n, int H, int W, uint32_t* bits_out, hipStream_t s);
+// ------------------------------------------------------------------ windows.hip: window-sized bit-packed masks -> full-frame rows / label stack
+// table: saber_window_mask records on the device (include/saber_amd_kernels.h); place: out (n,H,W32), every word written once; stack: out
+// (count,H,W) of elem_bytes, plane i = (first + i + 1) * mask first + i, every element written once.  One launch each, nothing for n / count == 0.
+struct saber_window_mask;
+const char* launch_window_place(const uint32_t* src, const saber_window_mask* table, int n, int H, int W, uint32_t* out, hipStream_t s);
+const char* launch_window_stack(const uint32_t* src, const saber_window_mask* table, int first, int count, int H, int W, int elem_bytes, void* out,
+                                hipStream_t s);
 const char* launch_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res,
                                     hipStream_t s);
 const char* launch_patch_embed(const float* pix, const float* wt, const float* bias, const float* pos, float* out, int n_images,

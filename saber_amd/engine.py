@@ -398,6 +398,61 @@ class Engine:
         self._check(self.lib.saber_mask_pair_intersections(self.h, _ptr(bits) if n else None, n, H, W, _ptr(inter) if n else None, _stream()))
         return inter
 
+    # ------------------------------------------------------------------ sliding-window masks (csrc/windows.hip)
+    def _check_window_src(self, who: str, src):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"saber_amd.Engine.{who} needs a ROCm device; there is no CPU fallback")
+        if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in (torch.int32, torch.uint32) or src.dim() != 1:
+            raise ValueError(f"{who}: src must be a 1-D int32 device tensor of packed window rows")
+        if src.device != self.device:
+            raise ValueError(f"{who}: src is on {src.device}, the engine on {self.device}")
+        return src.contiguous()
+
+    def place_window_masks(self, src: torch.Tensor, table, H: int, W: int) -> torch.Tensor:
+        """Window-sized bit-packed masks in full-frame rows (include/saber_amd.h: saber_place_window_masks): the generator's layout of what
+        saber2D.rasterize_masks builds as bool arrays.  src: 1-D int32 device tensor, table: the n records (src_word, y0, x0, h, w) - a
+        sequence of tuples or a _lib.window_table.  Returns (n, H, ceil(W/32)) int32, zero outside each window.  Every record is checked
+        on the host (ValueError naming it) before anything is launched.  One launch, no host synchronisation."""
+        src = self._check_window_src("place_window_masks", src)
+        n = len(table)
+        tab = _lib.window_table(table)
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError(f"place_window_masks: H and W must be at least 1, got {H} x {W}")
+        out = torch.empty((n, H, (W + 31) // 32), dtype=torch.int32, device=self.device)
+        self._check(self.lib.saber_place_window_masks(self.h, _ptr(src), src.numel(), tab, n, H, W, _ptr(out), _stream()))
+        return out
+
+    def window_label_stack(self, src: torch.Tensor, table, H: int, W: int, first: int = 0, count: Optional[int] = None,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Planes first .. first + count - 1 of the filters.masks.masks_to_array stack of the n window masks of `table`, written straight from
+        the window rows (include/saber_amd.h: saber_window_label_stack): plane i holds first + i + 1 where mask first + i covers the pixel.
+        The element type follows the TOTAL number of masks n, as masks_to_array's does: uint8 below 256, then 2 bytes below 65536, then 4 -
+        returned as uint8 / int16 / int32 (torch has no unsigned 16- / 32-bit arithmetic; view the download as np.uint16 / np.uint32).
+        out: an optional contiguous (count,H,W) device tensor of that type to write into.  One launch, no host synchronisation."""
+        src = self._check_window_src("window_label_stack", src)
+        n = len(table)
+        first = int(first)
+        count = n - first if count is None else int(count)
+        H, W = int(H), int(W)
+        if first < 0 or count < 0 or first + count > n:
+            raise ValueError(f"window_label_stack: planes {first} .. {first + count} of {n} masks")
+        if H < 1 or W < 1:
+            raise ValueError(f"window_label_stack: H and W must be at least 1, got {H} x {W}")
+        dtype = window_stack_dtype(n)
+        if out is None:
+            out = torch.empty((count, H, W), dtype=dtype, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != dtype or tuple(out.shape) != (count, H, W)
+              or not out.is_contiguous()):
+            raise ValueError(f"window_label_stack: out must be a contiguous ({count},{H},{W}) {dtype} tensor on {self.device}")
+        self._check(self.lib.saber_window_label_stack(self.h, _ptr(src), src.numel(), _lib.window_table(table), n, first, count, H, W,
+                                                      out.element_size(), _ptr(out), _stream()))
+        return out
+
+    def unpack_masks(self, bits: torch.Tensor, W: int) -> np.ndarray:
+        """(n,H,W32) int32 device stack -> (n,H,W) bool numpy, unpacked on the device (unpack_bits below)"""
+        return unpack_bits(self._check_packed("unpack_masks", bits, W), int(W))
+
     def separate_masks(self, planes: torch.Tensor, min_mask_area: int = 100):
         """utils.separate_masks on the device.  planes: (Z,H,W) uint16 / int16 device tensor of per-slice label planes.
         Returns ((Z,H,W) int32 device tensor holding the uint32 labels, number of labels)."""
@@ -662,6 +717,12 @@ def lowres_cleanup_env_defaults():
         _check_cleanup_areas(var, v, 0)
         out.append(v)
     return tuple(out)
+
+
+def window_stack_dtype(n: int) -> torch.dtype:
+    """the element type of Engine.window_label_stack for n masks in all: filters.masks.masks_to_array's rule (uint8 below 256 masks, uint16
+    below 65536, uint32 beyond) in the torch types that carry those bytes"""
+    return torch.uint8 if n < 256 else (torch.int16 if n < 65536 else torch.int32)
 
 
 def unpack_bits(bits: torch.Tensor, W: int) -> np.ndarray:

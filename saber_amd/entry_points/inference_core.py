@@ -75,7 +75,10 @@ def segment_tomogram_core(run, voxel_size: float, tomogram_algorithm: str, segme
 
 
 def segment_micrograph_core(input: str, output: str, scale_factor: float, target_resolution: float, display_image: bool,
-                            use_sliding_window: bool, gpu_id, models):
+                            use_sliding_window: bool, gpu_id, models, device_windows: bool = False):
+    """device_windows: with use_sliding_window, keep the window masks on the device (saber2D.segment_windows_device) and write the label
+    stack from WindowMasks.to_array_host(): no per-mask full-frame bool array is made on the host.  segmenter.masks then holds the
+    records without `segmentation`, segmenter.window_masks the device result.  The stored datasets are those of the host route."""
     import os
 
     from saber_amd.filters.downsample import FourierRescale2D
@@ -91,10 +94,17 @@ def segment_micrograph_core(input: str, output: str, scale_factor: float, target
         image = FourierRescale2D.run(image, target_resolution / pixel_size)
     elif scale_factor is not None:
         image = FourierRescale2D.run(image, scale_factor)
-    segmenter.segment(image, target_class=models.get("target_class", -1), display=False, use_sliding_window=use_sliding_window)
+    if device_windows and use_sliding_window:
+        wm = segmenter.segment_windows_device(image)
+        segmenter.target_class = models.get("target_class", -1)
+        segmenter.image0 = segmenter.image = image
+        segmenter.masks, segmenter.window_masks = wm.records, wm
+        masks = wm.to_array_host()
+    else:
+        segmenter.segment(image, target_class=models.get("target_class", -1), display=False, use_sliding_window=use_sliding_window)
+        masks = mask_filters.masks_to_array(segmenter.masks)
     if isinstance(pixel_size, np.ndarray):
         pixel_size = pixel_size.item()
-    masks = mask_filters.masks_to_array(segmenter.masks)
     pixel_size = pixel_size / 10 if pixel_size is not None else 1        # Angstrom -> nanometer (inference_core.py:144-148)
     out_image = segmenter.image
     if out_image.ndim == 3:

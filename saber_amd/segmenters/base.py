@@ -34,6 +34,8 @@ class saber2D:
         self.save_button = False
         self.remove_repeating_masks = True
         self.device_consensus = False       # True: the classifier filter's consensus resolution runs on self.device (filters/masks.py, csrc/consensus2d.hip)
+        self.device_windows = False         # True: segment_image(use_sliding_window=True) keeps the window masks on self.device (segmenters/windows.py, csrc/windows.hip); same list
+        self.window_masks = None            # the WindowMasks of the last device_windows run
 
     def segment(self, image: np.ndarray, target_class: Optional[int] = None, text: Optional[str] = None,
                 threshold: Optional[float] = 0.5, display: bool = False, use_sliding_window: bool = False) -> list:
@@ -44,7 +46,10 @@ class saber2D:
     def segment_image(self, image: np.ndarray, display: bool = True, use_sliding_window: bool = False,
                       text_prompt: Optional[str] = None, threshold: Optional[float] = 0.5, target_class: Optional[int] = 1):
         self.target_class = target_class
-        if use_sliding_window:
+        if use_sliding_window and self.device_windows:
+            self.window_masks = self.segment_windows_device(image, text_prompt=text_prompt, threshold=threshold)
+            self.masks = self.window_masks.dicts()
+        elif use_sliding_window:
             collected = []
             for (y1, x1, y2, x2) in self.get_sliding_windows(image.shape):
                 window = image[y1:y2, x1:x2]
@@ -64,6 +69,17 @@ class saber2D:
         # display / save hooks of the reference (matplotlib viewers) are outside the hot-path build
         self.image = image
         return self.masks
+
+    @torch.inference_mode()
+    def segment_windows_device(self, image: np.ndarray, text_prompt: Optional[str] = None, threshold: Optional[float] = 0.5):
+        """The sliding-window branch of segment_image with the masks left on the device (segmenters/windows.py): returns a WindowMasks
+        whose dicts() is the list the host branch returns.  Without a classifier only: upstream's branch is not defined with one (the
+        classifier's dicts carry no `offset`, rasterize_masks raises KeyError there)."""
+        if self.classifier is not None:
+            raise ValueError("segment_windows_device: the sliding-window branch is not defined with a classifier")
+        from saber_amd.segmenters import windows
+        return windows.segment_windows(image, self.get_sliding_windows(image.shape), self.adapter._generator(), self.min_mask_area,
+                                       remove_repeating_masks=self.remove_repeating_masks)
 
     def _apply_classifier(self, image, masks):
         masks = [m for m in masks if m["area"] >= self.min_mask_area]
