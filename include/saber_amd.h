@@ -21,6 +21,8 @@
  *       <- the paint loop of propagationSegmenter.slice_by_slice      saber/segmenters/propagation.py:185-186
  *   saber_separate_masks
  *       <- separate_masks(vol_masks, min_mask_area)                   saber/segmenters/utils.py:88-131
+ *   saber_cc_chunk_label / saber_cc_seam_pairs / saber_cc_chunk_roots / saber_cc_chunk_finish
+ *       <- the same separate_masks, one z-chunk per rank              saber/segmenters/utils.py:88-131
  *   saber_classifier_*
  *       <- Predictor(model_config, model_weights).predict / SAM2Classifier.forward
  *                                                                     saber/classifier/models/predictor.py:117-175, SAM2.py:118-197
@@ -307,6 +309,36 @@ int saber_mask_pair_intersections(saber_engine* e, const uint32_t* bits_dev, int
  * Z*H*W < 2^31.  Synchronises the stream (the label count is returned). */
 int saber_separate_masks(saber_engine* e, const uint16_t* planes_dev, int Z, int H, int W, int min_mask_area, uint32_t* out_dev,
                          int* out_n_labels, void* stream);
+
+/* ---- the same stitch with the volume cut into consecutive z-chunks (one per rank, or one after the other on one device), csrc/cc3d.hip;
+ * the host side is saber_amd/segmenters/stitch.py.  Only a created handle is needed.  A chunk's roots are chunk-local voxel indices
+ * (a component's first voxel in C-order scan of the chunk); root + z0*H*W is the voxel's index in the whole volume, which must stay
+ * below 2^31 - 1 as for saber_separate_masks.
+ *
+ * saber_cc_chunk_label: the labelling of saber_separate_masks on one chunk, into caller-owned buffers.  planes_dev: (Z,H,W) uint16;
+ * lab_dev, sizes_dev: (Z,H,W) uint32.  On return (enqueued, no synchronisation) lab[v] = root of v or 0xffffffff for background, and
+ * sizes[root] = voxels of the root's component inside the chunk (0 at every other index). */
+int saber_cc_chunk_label(saber_engine* e, const uint16_t* planes_dev, int Z, int H, int W, uint32_t* lab_dev, uint32_t* sizes_dev, void* stream);
+/* saber_cc_seam_pairs: what touches across the seam between a chunk's last plane (a) and the next chunk's first plane (b).
+ * a_roots_dev, b_roots_dev: (H,W) uint32 planes of `lab`; a_offset / b_offset (z0*H*W of either chunk) are added to the roots.
+ * pairs_dev: capacity x 2 uint32, receives rows (root in a, root in b) for every foreground pixel of a and every foreground pixel of b within
+ * |dy| <= 1, |dx| <= 1, under the merge rule of the labelling (per row the centre neighbour if it is foreground, else the two diagonals).
+ * The rows come in no particular order and may repeat; as a set they do not depend on the order of execution.  *out_count = rows found.
+ * When that exceeds capacity nothing past capacity is written and the call returns SABER_ERR_CAPACITY with *out_count set: call again with
+ * room for all.  Synchronises the stream. */
+int saber_cc_seam_pairs(saber_engine* e, const uint32_t* a_roots_dev, const uint32_t* b_roots_dev, int H, int W, uint32_t a_offset, uint32_t b_offset,
+                        uint32_t* pairs_dev, int capacity, int* out_count, void* stream);
+/* saber_cc_chunk_roots: the chunk's roots with at least max(min_voxels, 1) voxels, except those in exclude_host (the roots that face a
+ * seam: their component may continue in another chunk), ascending, into roots_out_host.  sizes[root] is cleared for the excluded and the
+ * smaller ones (id 0 until saber_cc_chunk_finish says otherwise).  *out_count = roots found; beyond capacity SABER_ERR_CAPACITY with
+ * *out_count set, and the call may be repeated.  Synchronises the stream. */
+int saber_cc_chunk_roots(saber_engine* e, const uint32_t* lab_dev, uint32_t* sizes_dev, int Z, int H, int W, uint32_t min_voxels,
+                         const uint32_t* exclude_host, int n_exclude, uint32_t* roots_out_host, int capacity, int* out_count, void* stream);
+/* saber_cc_chunk_finish: sizes[roots_host[i]] = ids_host[i] for the k listed roots (each must be a root of `lab`), then
+ * sizes[v] = sizes[root of v], 0 for background: sizes_dev then holds the chunk's (Z,H,W) uint32 labels.  To be called after
+ * saber_cc_chunk_roots, with an id for every root that is to survive.  Synchronises the stream. */
+int saber_cc_chunk_finish(saber_engine* e, const uint32_t* lab_dev, uint32_t* sizes_dev, int Z, int H, int W, const uint32_t* roots_host,
+                          const uint32_t* ids_host, int k, void* stream);
 
 /* Per-label adaptive 3-D Gaussian smoothing of a label volume (replaces saber.filters.masks.fast_3d_gaussian_smoothing,
  * saber/filters/masks.py:230-287; applied to the segmenter's output by segment_tomogram_core, saber/entry_points/inference_core.py:68-74

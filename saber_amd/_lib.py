@@ -108,6 +108,10 @@ SIGNATURES = {
     "saber_place_window_masks": (_i, [_vp, _vp, C.c_int64, C.POINTER(WindowMask), _i, _i, _i, _vp, _vp]),
     "saber_window_label_stack": (_i, [_vp, _vp, C.c_int64, C.POINTER(WindowMask), _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "saber_separate_masks": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
+    "saber_cc_chunk_label": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "saber_cc_seam_pairs": (_i, [_vp, _vp, _vp, _i, _i, C.c_uint32, C.c_uint32, _vp, _i, C.POINTER(_i), _vp]),
+    "saber_cc_chunk_roots": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_uint32, _vp, _i, _vp, _i, C.POINTER(_i), _vp]),
+    "saber_cc_chunk_finish": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "saber_smooth_labels": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, C.POINTER(_i), _vp]),
     "saber_gaussian_smoothing_3d": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp]),
     "saber_morph_ball_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

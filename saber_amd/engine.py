@@ -463,6 +463,95 @@ class Engine:
         self._check(self.lib.saber_separate_masks(self.h, _ptr(planes), Z, H, W, int(min_mask_area), _ptr(out), C.byref(n), _stream()))
         return out, n.value
 
+    # ------------------------------------------------------------------ the stitch over z-chunks (csrc/cc3d.hip, segmenters/stitch.py)
+    def _check_chunk(self, who: str, lab: torch.Tensor, sizes: torch.Tensor):
+        for name, t in (("lab", lab), ("sizes", sizes)):
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32 or t.dim() != 3 or not t.is_contiguous()
+                    or t.numel() == 0):
+                raise ValueError(f"{who}: {name} must be a non-empty contiguous (Z,H,W) int32 tensor on {self.device}")
+        if lab.shape != sizes.shape:
+            raise ValueError(f"{who}: lab {tuple(lab.shape)} and sizes {tuple(sizes.shape)} differ in shape")
+        return lab.shape
+
+    @staticmethod
+    def _root_list(who: str, what: str, roots) -> np.ndarray:
+        a = np.asarray(roots)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError(f"{who}: {what} must hold voxel indices of the chunk")
+        return np.ascontiguousarray(a.reshape(-1), dtype=np.uint32)
+
+    def cc_chunk_label(self, planes: torch.Tensor):
+        """The labelling of separate_masks on one z-chunk.  planes: (Z,H,W) uint16 / int16 device tensor.  Returns (lab, sizes), both
+        (Z,H,W) int32 holding uint32: lab[v] = the chunk-local root of v (its component's first voxel in scan order; -1 = background),
+        sizes[root] = the component's voxels inside the chunk.  No host synchronisation."""
+        if (not isinstance(planes, torch.Tensor) or planes.device != self.device or planes.dim() != 3 or not planes.is_contiguous()
+                or planes.dtype not in (torch.uint16, torch.int16) or planes.numel() == 0):
+            raise ValueError(f"cc_chunk_label: planes must be a non-empty contiguous (Z,H,W) uint16 / int16 tensor on {self.device}")
+        Z, H, W = planes.shape
+        lab = torch.empty((Z, H, W), dtype=torch.int32, device=self.device)
+        sizes = torch.empty((Z, H, W), dtype=torch.int32, device=self.device)
+        self._check(self.lib.saber_cc_chunk_label(self.h, _ptr(planes), Z, H, W, _ptr(lab), _ptr(sizes), _stream()))
+        return lab, sizes
+
+    def cc_seam_pairs(self, a_roots: torch.Tensor, b_roots: torch.Tensor, a_offset: int = 0, b_offset: int = 0,
+                      capacity: Optional[int] = None) -> np.ndarray:
+        """The roots that touch across a seam.  a_roots: a chunk's last (H,W) plane of `lab`, b_roots: the next chunk's first one (int32
+        device tensors, -1 = background); the offsets (z0 * H * W of either chunk) turn chunk-local roots into global voxel indices.
+        Returns the (k,2) int64 array of unique rows (root in a, root in b), sorted.  capacity: rows of the device buffer of the first
+        attempt (default H * W); a seam with more is run once more with the count the kernel reported."""
+        for name, t in (("a_roots", a_roots), ("b_roots", b_roots)):
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous()
+                    or t.numel() == 0):
+                raise ValueError(f"cc_seam_pairs: {name} must be a non-empty contiguous (H,W) int32 tensor on {self.device}")
+        if a_roots.shape != b_roots.shape:
+            raise ValueError(f"cc_seam_pairs: the planes differ in shape, {tuple(a_roots.shape)} and {tuple(b_roots.shape)}")
+        H, W = a_roots.shape
+        cap = H * W if capacity is None else int(capacity)
+        if cap < 0 or not 0 <= int(a_offset) <= 0x7FFFFFFF or not 0 <= int(b_offset) <= 0x7FFFFFFF:
+            raise ValueError("cc_seam_pairs: capacity and offsets must not be negative (offsets below 2^31)")
+        n = C.c_int(0)
+        for _ in range(2):
+            buf = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=self.device)
+            st = self.lib.saber_cc_seam_pairs(self.h, _ptr(a_roots), _ptr(b_roots), H, W, int(a_offset), int(b_offset), _ptr(buf), cap, C.byref(n),
+                                              _stream())
+            if st != _lib.SABER_ERR_CAPACITY:
+                break
+            cap = n.value                      # the kernel counted every pair: room for all of them now
+        self._check(st)
+        rows = buf[:n.value].cpu().numpy().view(np.uint32).astype(np.int64)
+        return np.unique(rows, axis=0) if rows.size else rows.reshape(0, 2)
+
+    def cc_chunk_roots(self, lab: torch.Tensor, sizes: torch.Tensor, min_voxels: int, exclude=()) -> np.ndarray:
+        """The chunk-local roots with at least max(min_voxels, 1) voxels that are not in `exclude` (the roots that face a seam), ascending
+        (int64).  sizes[root] is cleared for the excluded and the smaller roots."""
+        Z, H, W = self._check_chunk("cc_chunk_roots", lab, sizes)
+        ex = self._root_list("cc_chunk_roots", "exclude", exclude)
+        if not 0 <= int(min_voxels) <= 0xFFFFFFFF:
+            raise ValueError(f"cc_chunk_roots: min_voxels {min_voxels} out of range")
+        n = C.c_int(0)
+        cap = 4096
+        for _ in range(2):
+            out = np.empty(cap, dtype=np.uint32)
+            st = self.lib.saber_cc_chunk_roots(self.h, _ptr(lab), _ptr(sizes), Z, H, W, int(min_voxels), ex.ctypes.data_as(C.c_void_p) if ex.size else None,
+                                               int(ex.size), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), _stream())
+            if st != _lib.SABER_ERR_CAPACITY or n.value <= cap:
+                break
+            cap = n.value                      # the clearing is idempotent: the call may be repeated
+        self._check(st)
+        return out[:n.value].astype(np.int64)
+
+    def cc_chunk_finish(self, lab: torch.Tensor, sizes: torch.Tensor, roots, ids) -> torch.Tensor:
+        """Gives the listed chunk-local roots their ids and relabels the chunk: returns `sizes`, now the (Z,H,W) int32 tensor holding the
+        chunk's uint32 labels (every root not listed, and the background, is 0).  To be called after cc_chunk_roots."""
+        Z, H, W = self._check_chunk("cc_chunk_finish", lab, sizes)
+        r = self._root_list("cc_chunk_finish", "roots", roots)
+        i = self._root_list("cc_chunk_finish", "ids", ids)
+        if r.size != i.size:
+            raise ValueError(f"cc_chunk_finish: {r.size} roots and {i.size} ids")
+        self._check(self.lib.saber_cc_chunk_finish(self.h, _ptr(lab), _ptr(sizes), Z, H, W, r.ctypes.data_as(C.c_void_p) if r.size else None,
+                                                   i.ctypes.data_as(C.c_void_p) if i.size else None, int(r.size), _stream()))
+        return sizes
+
     def smooth_labels(self, labels: torch.Tensor, scale: float = 0.075):
         """filters.masks.fast_3d_gaussian_smoothing on the device.  labels: (Z,H,W) device tensor of uint8 / (u)int16 / (u)int32 label
         values (non-negative).  Returns ((Z,H,W) uint8 device tensor, number of labels found)."""

@@ -18,6 +18,7 @@ Engine.relabel_plane); the host decides from per-mask and per-component scalars 
 
 `segment_volume_sharded` is the multi-GPU form: rank r owns a contiguous z-chunk, planes are all-gathered
 (RCCL when the process group is NCCL, gloo in the CPU tests) and rank 0 (or every rank) stitches with separate_masks.
+With sharded_stitch=True the planes stay where they are: every rank labels its own chunk and the seams are joined (stitch.py).
 """
 from typing import Callable, Optional, Tuple
 
@@ -123,7 +124,8 @@ def shard_bounds(Z: int, world: int, rank: int) -> Tuple[int, int]:
 
 def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area: int = 100,
                            group=None, engine=None, smooth_scale: Optional[float] = None, timings: Optional[dict] = None,
-                           keep_on_device: bool = False, planes_out: Optional[list] = None) -> Optional[np.ndarray]:
+                           keep_on_device: bool = False, planes_out: Optional[list] = None, sharded_stitch: bool = False,
+                           gather: str = "all") -> Optional[np.ndarray]:
     """Slice-parallel slice_by_slice.  `volume` only supplies the shape (Z,H,W); `slice_fn(z)` returns the uint16
     label plane of slice z as a tensor on this rank's device.  All ranks receive every plane (all_gather of equal,
     zero-padded chunks); the (Z,H,W) uint32 stitched labels are returned (reference: utils.separate_masks).  With `engine`
@@ -135,7 +137,15 @@ def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area:
     `timings` (a dict, bench.py): filled with the seconds since entry at which this rank's chunk was segmented (`segmented`), every rank's
     planes had arrived (`gathered`) and the stitch had finished on the device (`stitched`), each behind a device synchronisation.
     `keep_on_device` (device stitch only): return the (Z,H,W) int32 device tensor that holds the uint32 labels instead of a host array;
-    `planes_out` (device stitch only): a list that receives the gathered (Z,H,W) int16 device tensor of label planes the stitch ran on."""
+    `planes_out` (device stitch only): a list that receives the gathered (Z,H,W) int16 device tensor of label planes the stitch ran on.
+    `sharded_stitch` (with `stitch`): the planes are NOT gathered.  Every rank labels its own z-chunk, the ranks exchange what touches a seam
+    (one root plane per rank and two short pickled records, segmenters/stitch.py) and every rank ends up with the final labels of its chunk,
+    bit-identical to the gathered stitch.  On the device with `engine` and device planes, else on the host (scipy).  `gather` then says
+    where the labels go: "all" - every rank returns the full uint32 volume, as without the option (all-gather of the label chunks; with
+    `keep_on_device` the int32 device tensor); "rank0" - rank 0 returns it, the other ranks None; "none" - (this rank's chunk of labels,
+    (z0, z1)): an int32 device tensor holding the uint32 labels for device planes, a uint32 array for CPU planes.  `smooth_scale` needs
+    the whole volume: ValueError.  `timings` also receives `labelled` (chunk labelled, seam record ready) and `resolved` (seams resolved,
+    ids known); `stitched` is the relabelled chunk, `gathered` the arrival of the label chunks, `labels` the count of the whole volume."""
     import time
     import torch.distributed as dist
     t_entry = time.perf_counter()
@@ -146,6 +156,12 @@ def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area:
                 torch.cuda.synchronize(dev_)
             timings[key] = time.perf_counter() - t_entry
     Z, H, W = volume.shape
+    sharded_stitch = bool(sharded_stitch) and stitch
+    if sharded_stitch:
+        if gather not in ("all", "rank0", "none"):
+            raise ValueError(f"segment_volume_sharded: gather must be 'all', 'rank0' or 'none', got {gather!r}")
+        if smooth_scale is not None:
+            raise ValueError("segment_volume_sharded: smooth_scale needs the whole volume on one rank; it cannot follow sharded_stitch")
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
     rank = dist.get_rank(group) if dist_on else 0
@@ -192,6 +208,23 @@ def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area:
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() and dist_on and dist.get_backend(group) == "nccl" else torch.device("cpu")
         local = torch.zeros((chunk, H, W), dtype=torch.int16, device=dev)
     stamp("segmented", dev)
+    if sharded_stitch:
+        from . import stitch as chunked
+        bounds = [shard_bounds(Z, world, r) for r in range(world)]
+        on_device = engine is not None and local.is_cuda
+        mine = local[:z1 - z0] if on_device else local[:z1 - z0].cpu()
+        labels, n_labels = chunked.stitch_rank(engine if on_device else None, mine, Z, H, W, bounds, rank, group, min_mask_area,
+                                               stamp=lambda key: stamp(key, dev))
+        stamp("stitched", dev)
+        if timings is not None:
+            timings["labels"] = n_labels
+        if gather == "none":
+            return labels, (z0, z1)
+        full = chunked.gather_labels(labels, Z, H, W, bounds, rank, group, gather)
+        stamp("gathered", dev)
+        if full is None:
+            return None
+        return full if keep_on_device and full.is_cuda else full.cpu().numpy().view(np.uint32)
     if world > 1:
         full = torch.empty((world * chunk, H, W), dtype=torch.int16, device=dev)
         # byte view: gloo (CPU tests) has no int16 collectives; RCCL moves the same bytes
