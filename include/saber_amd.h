@@ -29,6 +29,8 @@
  *   saber_smooth_labels / saber_gaussian_smoothing_3d
  *       <- fast_3d_gaussian_smoothing(volume, scale, deviceID)        saber/filters/masks.py:230-287
  *          gaussian_smoothing_3d(volume, sigma, device)               saber/filters/gaussian.py:76-138
+ *   saber_smooth_labels_chunk / saber_smooth_radius / saber_label_max / saber_label_counts
+ *       <- the same fast_3d_gaussian_smoothing, one z-chunk per rank  saber/filters/masks.py:230-287
  *   saber_consensus_components, saber_consensus_components_bits, saber_relabel_plane
  *       <- _consensus_based_resolution(image_shape, masks, confidences) saber/filters/masks.py:64-121
  *
@@ -349,6 +351,33 @@ int saber_cc_chunk_finish(saber_engine* e, const uint32_t* lab_dev, uint32_t* si
  * Only a created handle is needed (no weights / finalize).  Synchronises the stream (per-label statistics come back to the host). */
 int saber_smooth_labels(saber_engine* e, const void* labels_dev, int elem_bytes, int Z, int H, int W, double scale, uint8_t* out_dev,
                         int* out_n_labels, void* stream);
+
+/* saber_smooth_labels for one z-chunk of a volume that is spread over several ranks (saber_amd/segmenters/smooth.py): the result on the
+ * chunk's own planes, bit for bit what saber_smooth_labels gives there on the whole volume.  Three separate buffers, each (planes,H,W)
+ * of elem_bytes: own_dev the chunk's planes [z0, z1), lo_dev the lo_planes planes [z0 - lo_planes, z0) below it, hi_dev the hi_planes
+ * planes [z1, z1 + hi_planes) above it (a buffer of 0 planes may be NULL).  ids_host / counts_host: n_ids label values, ascending, with
+ * their voxel counts in the WHOLE volume - sigma, radius and taps come from these counts, bounding boxes from the three buffers.  Every
+ * label value found in the buffers must be listed.  A halo must hold at least the largest radius of the table (saber_smooth_radius)
+ * unless it ends at the volume's end (lo_is_volume_end: plane z0 - lo_planes is plane 0; hi_is_volume_end: the volume ends at
+ * z1 + hi_planes).  A label is convolved on the planes [z0 - r, z1 + r) only and skipped when its voxels there all lie on one side of
+ * the own planes.  out_dev: (own_planes,H,W) uint8; *out_n_labels = labels convolved.  Workspace: 4 B per OWN voxel + the fp32 boxes.
+ * SABER_ERR_INVALID ("smooth_labels_chunk: ..."): a label missing from the table, a short halo, label values above 2^22, a radius above
+ * 284, 2^31 - 1 voxels or more over the three buffers.  Synchronises the stream. */
+int saber_smooth_labels_chunk(saber_engine* e, const void* lo_dev, int lo_planes, const void* own_dev, int own_planes, const void* hi_dev,
+                              int hi_planes, int lo_is_volume_end, int hi_is_volume_end, int elem_bytes, int H, int W,
+                              const uint32_t* ids_host, const int64_t* counts_host, int n_ids, double scale, uint8_t* out_dev,
+                              int* out_n_labels, void* stream);
+
+/* The tap radius saber_smooth_labels / saber_smooth_labels_chunk use for a label of `count` voxels at `scale` (host arithmetic only, the
+ * function the drivers themselves call): what a caller sizes the halos of saber_smooth_labels_chunk with. */
+int saber_smooth_radius(int64_t count, double scale, int* out_radius);
+
+/* The counts saber_smooth_labels_chunk's table is summed from.  saber_label_max: *out_max = the largest value of n label elements.
+ * saber_label_counts: counts_dev[v] = voxels of label value v in the (Z,H,W) volume for 0 < v < n_counts, counts_dev[0] = 0 (the
+ * background is not counted); int64; every value of the volume must be below n_counts.  elem_bytes 1, 2 or 4 (unsigned).  Both synchronise the stream. */
+int saber_label_max(saber_engine* e, const void* labels_dev, int elem_bytes, int64_t n, uint32_t* out_max, void* stream);
+int saber_label_counts(saber_engine* e, const void* labels_dev, int elem_bytes, int Z, int H, int W, int n_counts, int64_t* counts_dev,
+                       void* stream);
 
 /* The separable filter itself on one 0/1 mask with a given sigma (saber/filters/gaussian.py:76-138): mask_dev (Z,H,W) uint8,
  * out_dev (Z,H,W) float32. */

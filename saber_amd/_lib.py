@@ -113,6 +113,10 @@ SIGNATURES = {
     "saber_cc_chunk_roots": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_uint32, _vp, _i, _vp, _i, C.POINTER(_i), _vp]),
     "saber_cc_chunk_finish": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "saber_smooth_labels": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, C.POINTER(_i), _vp]),
+    "saber_smooth_labels_chunk": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, C.c_double, _vp, C.POINTER(_i), _vp]),
+    "saber_smooth_radius": (_i, [C.c_int64, C.c_double, C.POINTER(_i)]),
+    "saber_label_max": (_i, [_vp, _vp, _i, C.c_int64, C.POINTER(C.c_uint32), _vp]),
+    "saber_label_counts": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "saber_gaussian_smoothing_3d": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp]),
     "saber_morph_ball_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "saber_components6_3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),

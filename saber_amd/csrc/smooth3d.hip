@@ -16,6 +16,10 @@
 //   5. sm_conv_axis<1>     field = conv_z(T2); field > 0.5 -> atomicMax(winner, v)   ("later label overwrites" = largest label)
 //   6. sm_cast             out = (uint8) winner  (the reference's result array is uint8: label values wrap modulo 256)
 // HBM-bound byte work: ~20 B per box voxel.  Each output sums its taps in ascending tap order with fma, as the CPU oracle does.
+//
+// One z-chunk of a volume that is spread over several ranks (saber_smooth_labels_chunk, at the end of this file): the same steps on
+// (planes below, own planes, planes above) in three buffers, with the counts of the whole volume handed in - sm_conv_x_seg reads its
+// rows through a segment table, sm_conv_z_own writes the winner of the own planes only.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -198,10 +202,113 @@ __global__ __launch_bounds__(256) void sm_cast_kernel(const uint32_t* __restrict
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[(n4 << 2) + threadIdx.x] = (uint8_t)winner[(n4 << 2) + threadIdx.x];
 }
 
+// ---- one z-chunk of a volume (saber_smooth_labels_chunk): the planes below, the own planes and the planes above lie in three buffers.
+// Planes are counted from the first plane of the lower halo; plane p lies in the last segment whose first[] <= p.
+struct SmSegs {
+    const void* base[3];
+    int first[3];
+};
+
+// sm_conv_x_kernel with the rows read through the segment table
+template <typename T>
+__global__ __launch_bounds__(256) void sm_conv_x_seg_kernel(SmSegs segs, int H, int W, const SmLabel* __restrict__ labels,
+                                                            const int* __restrict__ prefix, int n_labels, const float* __restrict__ taps,
+                                                            float* __restrict__ ws) {
+    extern __shared__ float sm_lds[];
+    const int li = sm_find(prefix, n_labels, blockIdx.x);
+    const SmLabel L = labels[li];
+    const int t = blockIdx.x - prefix[li];
+    const int xchunks = (L.dx + 63) / 64;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = (t / xchunks) * 4 + wave;                   // row of the box: z * dy + y
+    const int xc = (t % xchunks) * 64;
+    const int seg = 64 + 2 * L.r;
+    float* s = sm_lds + wave * seg;
+    const bool live = row < L.dz * L.dy;
+    if (live) {
+        const int z = L.z0 + row / L.dy, y = row % L.dy;
+        const bool s2 = z >= segs.first[2], s1 = z >= segs.first[1];
+        const void* base = s2 ? segs.base[2] : (s1 ? segs.base[1] : segs.base[0]);
+        const int zl = z - (s2 ? segs.first[2] : (s1 ? segs.first[1] : segs.first[0]));
+        const T* p = (const T*)base + ((int64_t)zl * H + (L.y0 + y)) * W + L.x0;
+        for (int i = lane; i < seg; i += 64) {
+            const int x = xc - L.r + i;
+            s[i] = (x >= 0 && x < L.dx && (uint32_t)p[x] == L.label) ? 1.0f : 0.0f;
+        }
+    }
+    __syncthreads();
+    if (!live || xc + lane >= L.dx) return;
+    const float* tp = taps + L.tap_off;
+    float acc = 0.0f;
+    for (int k = 0; k <= 2 * L.r; ++k) acc = fmaf(tp[k], s[lane + k], acc);
+    ws[L.ws_off + (int64_t)row * L.dx + xc + lane] = acc;
+}
+
+// sm_conv_axis_kernel<1, false> for the own planes of the box only: own[li] = {the box's first own plane (box-local), how many};
+// `winner` holds the own planes, own0 = the first of them in segment planes.  The sum of an output is that kernel's: taps ascending, fma.
+__global__ __launch_bounds__(256) void sm_conv_z_own_kernel(const SmLabel* __restrict__ labels, const int* __restrict__ prefix, int n_labels,
+                                                            const int2* __restrict__ own, const float* __restrict__ taps,
+                                                            const float* __restrict__ ws, int H, int W, int own0, uint32_t* __restrict__ winner) {
+    extern __shared__ float sm_lds[];
+    const int li = sm_find(prefix, n_labels, blockIdx.x);
+    const SmLabel L = labels[li];
+    const int2 O = own[li];
+    int t = blockIdx.x - prefix[li];
+    const int64_t st_axis = (int64_t)L.dy * L.dx;
+    const int xchunks = (L.dx + SM_TX - 1) / SM_TX, lchunks = (O.y + SM_TL - 1) / SM_TL;
+    const int xc = (t % xchunks) * SM_TX; t /= xchunks;
+    const int l0 = O.x + (t % lchunks) * SM_TL;
+    const int y = t / lchunks;
+    const int lend = O.x + O.y;
+    const float* src = ws + L.ws_off + (int64_t)L.dz * st_axis + (int64_t)y * L.dx;
+    const int rows = SM_TL + 2 * L.r;
+    const int xl = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    const bool xok = xc + xl < L.dx;
+    for (int j = grp; j < rows; j += 4) {
+        const int l = l0 - L.r + j;
+        sm_lds[j * SM_TX + xl] = (xok && l >= 0 && l < L.dz) ? src[l * st_axis + xc + xl] : 0.0f;
+    }
+    __syncthreads();
+    const int o0 = grp * SM_OPT;
+    if (!xok || l0 + o0 >= lend) return;
+    const float* tp = taps + L.tap_off;
+    float acc[SM_OPT];
+#pragma unroll
+    for (int o = 0; o < SM_OPT; ++o) acc[o] = 0.0f;
+    const float* col = sm_lds + o0 * SM_TX + xl;
+    for (int j = 0; j < 2 * L.r + SM_OPT; ++j) {
+        const float v = col[j * SM_TX];
+#pragma unroll
+        for (int o = 0; o < SM_OPT; ++o) acc[o] = fmaf(tp[j - o], v, acc[o]);
+    }
+#pragma unroll
+    for (int o = 0; o < SM_OPT; ++o) {
+        const int l = l0 + o0 + o;
+        if (l >= lend) break;
+        const int64_t g = ((int64_t)(L.z0 + l - own0) * H + (L.y0 + y)) * W + L.x0 + xc + xl;
+        if (acc[o] > 0.5f) atomicMax(winner + g, L.label);
+    }
+}
+
+// counts[v] = stats[v].count as int64 (saber_label_counts)
+__global__ __launch_bounds__(256) void sm_counts_kernel(const uint32_t* __restrict__ stats, int n, int64_t* __restrict__ counts) {
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v < n) counts[v] = (int64_t)stats[(size_t)v * 8];
+}
+
 // kernel size and taps exactly as gaussian.py:97-104 computes them (float32 taps, float32 normalisation)
-static int sm_make_taps(double sigma, std::vector<float>& out) {
+static int sm_kernel_size(double sigma) {
     int ks = (int)(2 * 3 * sigma + 1);
     if (ks % 2 == 0) ks += 1;
+    return ks;
+}
+// sigma of a label of `count` voxels: scale * the diameter of the sphere of that volume (masks.py:303-308)
+static double sm_label_sigma(double count, double scale) {
+    const double approx_diameter = 2.0 * std::pow((3.0 * count) / (4.0 * M_PI), 1.0 / 3.0);
+    return scale * approx_diameter;
+}
+static int sm_make_taps(double sigma, std::vector<float>& out) {
+    const int ks = sm_kernel_size(sigma);
     const int r = ks / 2;
     const float den = (float)(2.0 * sigma * sigma);
     std::vector<float> t(ks);
@@ -220,8 +327,10 @@ struct SmScratch {
     SmLabel* labels = nullptr;
     int* prefix = nullptr;
     float *taps = nullptr, *ws = nullptr;
+    int2* own = nullptr;                    // saber_smooth_labels_chunk only
     void release() {
         (void)hipFree(maxv); (void)hipFree(stats); (void)hipFree(winner); (void)hipFree(labels); (void)hipFree(prefix); (void)hipFree(taps); (void)hipFree(ws);
+        (void)hipFree(own);
     }
 };
 
@@ -301,10 +410,7 @@ static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, i
         L.dz = (int)(p[4] - p[1]) + 1; L.dy = (int)(p[5] - p[2]) + 1; L.dx = (int)(p[6] - p[3]) + 1;
         if (mode == 1) { L.z0 = L.y0 = L.x0 = 0; L.dz = Z; L.dy = H; L.dx = W; }      // the float field is wanted everywhere
         double sigma = fixed_sigma;
-        if (mode == 0) {
-            const double approx_diameter = 2.0 * std::pow((3.0 * (double)p[0]) / (4.0 * M_PI), 1.0 / 3.0);   // masks.py:303-308
-            sigma = scale * approx_diameter;
-        }
+        if (mode == 0) sigma = sm_label_sigma((double)p[0], scale);
         L.tap_off = (int)taps.size();
         L.r = sm_make_taps(sigma, taps);
         taps.insert(taps.end(), SM_OPT - 1, 0.0f);
@@ -405,4 +511,247 @@ extern "C" int saber_gaussian_smoothing_3d(saber_engine* e, const uint8_t* mask_
     if (!mask_dev || !out_dev || Z <= 0 || H <= 0 || W <= 0 || !(sigma > 0.0)) return eng_fail(e, SABER_ERR_INVALID, "gaussian_smoothing_3d: bad argument");
     if ((int64_t)Z * H * W >= (int64_t)0x7fffffff) return eng_fail(e, SABER_ERR_INVALID, "gaussian_smoothing_3d: volumes of 2^31 voxels or more are not supported");
     return sm_run(e, mask_dev, 1, Z, H, W, 0.0, sigma, 1, out_dev, nullptr, (hipStream_t)stream);
+}
+
+// ---- one z-chunk with its halos (header: saber_smooth_labels_chunk).  Why the own planes come out as the whole volume's: a label's
+// field on plane z depends on the planes z - r .. z + r only, all of which lie in the three buffers (halo >= r, or the volume ends);
+// sigma and taps come from the whole volume's count; every output sums its taps in ascending order with fma, and a larger box only
+// adds terms that are exactly +0.  The box here is the label's box inside the planes [own0 - r, own1 + r): outside it, on an own
+// plane, only one side of the kernel can meet the part of the mask that reaches that plane, so the field stays below 0.5 there, as
+// outside the whole volume's box.  A label whose voxels in those planes all lie below (or all above) the own planes has an empty
+// range of own planes inside its box and is skipped; one with voxels on both sides and none between (a "sandwich") is not.
+extern "C" int saber_smooth_radius(int64_t count, double scale, int* out_radius) {
+    if (!out_radius || count < 0 || !(scale > 0.0)) return SABER_ERR_INVALID;
+    *out_radius = count ? sm_kernel_size(sm_label_sigma((double)count, scale)) / 2 : 0;
+    return SABER_OK;
+}
+
+extern "C" int saber_smooth_labels_chunk(saber_engine* e, const void* lo_dev, int lo_planes, const void* own_dev, int own_planes,
+                                         const void* hi_dev, int hi_planes, int lo_is_volume_end, int hi_is_volume_end, int elem_bytes, int H,
+                                         int W, const uint32_t* ids_host, const int64_t* counts_host, int n_ids, double scale,
+                                         uint8_t* out_dev, int* out_n_labels, void* stream) {
+    if (!e) return SABER_ERR_INVALID;
+    if (!own_dev || !out_dev || own_planes <= 0 || lo_planes < 0 || hi_planes < 0 || (lo_planes && !lo_dev) || (hi_planes && !hi_dev) || H <= 0 ||
+        W <= 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) || !(scale > 0.0) || n_ids < 0 || (n_ids && (!ids_host || !counts_host)))
+        return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: bad argument");
+    const int64_t E = (int64_t)lo_planes + own_planes + hi_planes;
+    if (E * H * W >= (int64_t)0x7fffffff)
+        return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: 2^31 - 1 voxels or more over the three buffers are not supported");
+    hipStream_t s = (hipStream_t)stream;
+    const int own0 = lo_planes, own1 = lo_planes + own_planes;
+    const int64_t plane = (int64_t)H * W, n_own = (int64_t)own_planes * plane;
+    // ---- the table: ascending label values, positive counts; its largest radius is what the halos must hold
+    std::vector<int> radius(n_ids);
+    int rtab = 0;
+    for (int i = 0; i < n_ids; ++i) {
+        if (ids_host[i] == 0 || ids_host[i] > SM_MAX_LABEL || (i && ids_host[i] <= ids_host[i - 1]) || counts_host[i] <= 0)
+            return eng_fail(e, SABER_ERR_INVALID, ids_host[i] > SM_MAX_LABEL ? "smooth_labels_chunk: label values above 2^22 are not supported"
+                                                                            : "smooth_labels_chunk: the table must list ascending label values > 0 with counts > 0");
+        radius[i] = sm_kernel_size(sm_label_sigma((double)counts_host[i], scale)) / 2;
+        rtab = std::max(rtab, radius[i]);
+    }
+    if ((size_t)(SM_TL + 2 * rtab) * SM_TX * sizeof(float) > SM_LDS_LIMIT)
+        return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: Gaussian radius " + std::to_string(rtab) + " exceeds the supported 284 voxels");
+    if ((lo_planes < rtab && !lo_is_volume_end) || (hi_planes < rtab && !hi_is_volume_end))
+        return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: a halo of " + std::to_string(lo_planes < rtab && !lo_is_volume_end ? lo_planes : hi_planes) +
+                                                  " planes is shorter than the largest radius " + std::to_string(rtab) + " and is not the volume's end");
+    SmScratch S;
+    auto cleanup = [&]() { S.release(); };
+    ENG_DEVICE(e);
+    if (out_n_labels) *out_n_labels = 0;
+    const void* bufs[3] = {lo_dev, own_dev, hi_dev};
+    const int planes[3] = {lo_planes, own_planes, hi_planes};
+    const int first[3] = {0, own0, own1};
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
+    for (int b = 0; b < 3; ++b)
+        if (planes[b]) label_max(bufs[b], elem_bytes, nullptr, 0, planes[b] * plane, S.maxv, s);
+    uint32_t maxv = 0;
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, S.maxv, 4, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(out_dev, 0, (size_t)n_own, s));
+    if (maxv == 0) { ENG_HIP_CLEANUP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
+    if (maxv > SM_MAX_LABEL) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: label values above 2^22 are not supported"); }
+    // ---- count + bounding box per label value and buffer (z local to the buffer)
+    const size_t n_stats = (size_t)maxv + 1;
+    std::vector<uint32_t> st(3 * n_stats * 8);
+    for (size_t v = 0; v < 3 * n_stats; ++v) { uint32_t* p = &st[v * 8]; p[0] = 0; p[1] = p[2] = p[3] = 0xffffffffu; p[4] = p[5] = p[6] = p[7] = 0; }
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.stats, 3 * n_stats * 32));
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.stats, st.data(), 3 * n_stats * 32, hipMemcpyHostToDevice, s));
+    for (int b = 0; b < 3; ++b)
+        if (planes[b]) label_stats(bufs[b], elem_bytes, nullptr, planes[b], H, W, S.stats + (size_t)b * n_stats * 8, s);
+    ENG_HIP_CLEANUP(e, hipGetLastError());
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(st.data(), S.stats, 3 * n_stats * 32, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    // ---- host: per label value the box inside [own0 - r, own1 + r) and its own planes, ascending label value
+    std::vector<SmLabel> labs;
+    std::vector<int2> owns;
+    std::vector<float> taps(SM_OPT - 1, 0.0f);
+    int64_t biggest = 0;
+    int ti = 0;
+    for (size_t v = 1; v < n_stats; ++v) {
+        const uint32_t* q[3] = {&st[v * 8], &st[(n_stats + v) * 8], &st[(2 * n_stats + v) * 8]};
+        if (!q[0][0] && !q[1][0] && !q[2][0]) continue;
+        while (ti < n_ids && ids_host[ti] < v) ++ti;
+        if (ti == n_ids || ids_host[ti] != v) {
+            cleanup();
+            return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: label value " + std::to_string(v) + " is not in the table");
+        }
+        const int r = radius[ti];
+        const int w0 = std::max(0, own0 - r), w1 = (int)std::min<int64_t>(E, (int64_t)own1 + r);       // the planes this label is read on
+        // per buffer: present inside the window?  (segment planes; the lower halo lies below w1, the upper one above w0)
+        const bool in_lo = q[0][0] && (int)q[0][4] + first[0] >= w0;
+        const bool in_own = q[1][0] != 0;
+        const bool in_hi = q[2][0] && (int)q[2][1] + first[2] < w1;
+        if (!in_own && !(in_lo && in_hi)) continue;                 // all on one side of the own planes, or further than r: skipped
+        const bool in[3] = {in_lo, in_own, in_hi};
+        int zlo = 0x7fffffff, zhi = -1, ylo = 0x7fffffff, yhi = -1, xlo = 0x7fffffff, xhi = -1;
+        for (int b = 0; b < 3; ++b) {
+            if (!in[b]) continue;
+            zlo = std::min(zlo, (int)q[b][1] + first[b]); zhi = std::max(zhi, (int)q[b][4] + first[b]);
+            ylo = std::min(ylo, (int)q[b][2]); yhi = std::max(yhi, (int)q[b][5]);
+            xlo = std::min(xlo, (int)q[b][3]); xhi = std::max(xhi, (int)q[b][6]);
+        }
+        zlo = std::max(zlo, w0); zhi = std::min(zhi, w1 - 1);
+        const int o_first = std::max(zlo, own0), o_last = std::min(zhi, own1 - 1);
+        if (o_first > o_last) continue;
+        zlo = std::max(zlo, o_first - r); zhi = std::min(zhi, o_last + r);      // planes no own output of the box reads
+        SmLabel L;
+        L.label = (uint32_t)v;
+        L.z0 = zlo; L.y0 = ylo; L.x0 = xlo;
+        L.dz = zhi - zlo + 1; L.dy = yhi - ylo + 1; L.dx = xhi - xlo + 1;
+        L.tap_off = (int)taps.size();
+        L.r = sm_make_taps(sm_label_sigma((double)counts_host[ti], scale), taps);
+        taps.insert(taps.end(), SM_OPT - 1, 0.0f);
+        L.ws_off = 0;
+        biggest = std::max(biggest, (int64_t)L.dz * L.dy * L.dx);
+        labs.push_back(L);
+        owns.push_back(make_int2(o_first - zlo, o_last - o_first + 1));
+    }
+    if (out_n_labels) *out_n_labels = (int)labs.size();
+    if (labs.empty()) { ENG_HIP_CLEANUP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
+    // ---- groups of labels whose two fp32 boxes fit the workspace, as sm_run forms them; the winner covers the own planes only
+    int64_t total = 0;
+    for (auto& L : labs) total += 2 * (int64_t)L.dz * L.dy * L.dx;
+    const int64_t ws_floats = std::min(total, std::max<int64_t>(2 * biggest, (int64_t)1 << 28));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.ws, (size_t)ws_floats * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.taps, taps.size() * 4));
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.labels, labs.size() * sizeof(SmLabel)));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.own, labs.size() * sizeof(int2)));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.prefix, 3 * (labs.size() + 1) * sizeof(int)));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.winner, (size_t)n_own * 4));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.winner, 0, (size_t)n_own * 4, s));
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_z_own_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    SmSegs segs;
+    for (int b = 0; b < 3; ++b) { segs.base[b] = bufs[b]; segs.first[b] = first[b]; }
+    std::vector<int> prefix;
+    const size_t stride = labs.size() + 1;
+    size_t g0 = 0;
+    while (g0 < labs.size()) {
+        size_t g1 = g0;
+        int64_t used = 0;
+        int grmax = 0;
+        int64_t tiles[3] = {0, 0, 0};
+        prefix.assign(3 * stride, 0);
+        while (g1 < labs.size()) {
+            SmLabel& L = labs[g1];
+            const int64_t v2 = 2 * (int64_t)L.dz * L.dy * L.dx;
+            if (g1 > g0 && used + v2 > ws_floats) break;
+            const int64_t xch = (L.dx + 63) / 64;
+            const int64_t tx = (((int64_t)L.dz * L.dy + 3) / 4) * xch;
+            const int64_t ty = (int64_t)L.dz * ((L.dy + SM_TL - 1) / SM_TL) * xch;
+            const int64_t tz = (int64_t)L.dy * ((owns[g1].y + SM_TL - 1) / SM_TL) * xch;
+            if (tiles[0] + tx > 0x7fffffff || tiles[1] + ty > 0x7fffffff || tiles[2] + tz > 0x7fffffff) {
+                if (g1 == g0) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: label too large"); }
+                break;
+            }
+            L.ws_off = used;
+            used += v2;
+            grmax = std::max(grmax, L.r);
+            const size_t i = g1 - g0;
+            prefix[0 * stride + i] = (int)tiles[0]; prefix[1 * stride + i] = (int)tiles[1]; prefix[2 * stride + i] = (int)tiles[2];
+            tiles[0] += tx; tiles[1] += ty; tiles[2] += tz;
+            ++g1;
+        }
+        const int ng = (int)(g1 - g0);
+        for (int a = 0; a < 3; ++a) prefix[a * stride + ng] = (int)tiles[a];
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.labels, labs.data() + g0, (size_t)ng * sizeof(SmLabel), hipMemcpyHostToDevice, s));
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.own, owns.data() + g0, (size_t)ng * sizeof(int2), hipMemcpyHostToDevice, s));
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.prefix, prefix.data(), prefix.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        const size_t lds_x = (size_t)4 * (64 + 2 * grmax) * sizeof(float);
+        if (elem_bytes == 1)
+            hipLaunchKernelGGL(sm_conv_x_seg_kernel<uint8_t>, dim3((unsigned)tiles[0]), dim3(256), lds_x, s, segs, H, W, (const SmLabel*)S.labels,
+                               (const int*)S.prefix, ng, (const float*)S.taps, S.ws);
+        else if (elem_bytes == 2)
+            hipLaunchKernelGGL(sm_conv_x_seg_kernel<uint16_t>, dim3((unsigned)tiles[0]), dim3(256), lds_x, s, segs, H, W, (const SmLabel*)S.labels,
+                               (const int*)S.prefix, ng, (const float*)S.taps, S.ws);
+        else
+            hipLaunchKernelGGL(sm_conv_x_seg_kernel<uint32_t>, dim3((unsigned)tiles[0]), dim3(256), lds_x, s, segs, H, W, (const SmLabel*)S.labels,
+                               (const int*)S.prefix, ng, (const float*)S.taps, S.ws);
+        const size_t lds = (size_t)(SM_TL + 2 * grmax) * SM_TX * sizeof(float);
+        hipLaunchKernelGGL((sm_conv_axis_kernel<0, false>), dim3((unsigned)tiles[1]), dim3(256), lds, s, (const SmLabel*)S.labels,
+                           (const int*)(S.prefix + stride), ng, (const float*)S.taps, S.ws, H, W, (uint32_t*)nullptr, (float*)nullptr);
+        hipLaunchKernelGGL(sm_conv_z_own_kernel, dim3((unsigned)tiles[2]), dim3(256), lds, s, (const SmLabel*)S.labels,
+                           (const int*)(S.prefix + 2 * stride), ng, (const int2*)S.own, (const float*)S.taps, (const float*)S.ws, H, W, own0, S.winner);
+        ENG_HIP_CLEANUP(e, hipGetLastError());
+        ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                    // the descriptor / prefix host buffers are reused by the next group
+        g0 = g1;
+    }
+    hipLaunchKernelGGL(sm_cast_kernel, dim3((unsigned)std::min<int64_t>((n_own / 4 + 255) / 256 + 1, 1 << 16)), dim3(256), 0, s,
+                       (const uint32_t*)S.winner, out_dev, n_own);
+    ENG_HIP_CLEANUP(e, hipGetLastError());
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    cleanup();
+    return SABER_OK;
+}
+
+extern "C" int saber_label_max(saber_engine* e, const void* labels_dev, int elem_bytes, int64_t n, uint32_t* out_max, void* stream) {
+    if (!e) return SABER_ERR_INVALID;
+    if (!labels_dev || !out_max || n <= 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4))
+        return eng_fail(e, SABER_ERR_INVALID, "label_max: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    SmScratch S;
+    auto cleanup = [&]() { S.release(); };
+    ENG_DEVICE(e);
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
+    label_max(labels_dev, elem_bytes, nullptr, 0, n, S.maxv, s);
+    ENG_HIP_CLEANUP(e, hipGetLastError());
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(out_max, S.maxv, 4, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    cleanup();
+    return SABER_OK;
+}
+
+extern "C" int saber_label_counts(saber_engine* e, const void* labels_dev, int elem_bytes, int Z, int H, int W, int n_counts, int64_t* counts_dev,
+                                  void* stream) {
+    if (!e) return SABER_ERR_INVALID;
+    if (!labels_dev || !counts_dev || Z <= 0 || H <= 0 || W <= 0 || n_counts <= 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4))
+        return eng_fail(e, SABER_ERR_INVALID, "label_counts: bad argument");
+    if ((int64_t)Z * H * W >= (int64_t)0x7fffffff) return eng_fail(e, SABER_ERR_INVALID, "label_counts: volumes of 2^31 voxels or more are not supported");
+    if ((int64_t)n_counts > (int64_t)SM_MAX_LABEL + 1) return eng_fail(e, SABER_ERR_INVALID, "label_counts: label values above 2^22 are not supported");
+    hipStream_t s = (hipStream_t)stream;
+    SmScratch S;
+    auto cleanup = [&]() { S.release(); };
+    ENG_DEVICE(e);
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
+    label_max(labels_dev, elem_bytes, nullptr, 0, (int64_t)Z * H * W, S.maxv, s);
+    uint32_t maxv = 0;
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, S.maxv, 4, hipMemcpyDeviceToHost, s));
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    if (maxv >= (uint32_t)n_counts) {                                // the statistics kernel indexes its table by label value
+        cleanup();
+        return eng_fail(e, SABER_ERR_INVALID, "label_counts: label value " + std::to_string(maxv) + " does not fit a table of " + std::to_string(n_counts));
+    }
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.stats, (size_t)n_counts * 32));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.stats, 0, (size_t)n_counts * 32, s));
+    label_stats(labels_dev, elem_bytes, nullptr, Z, H, W, S.stats, s);
+    hipLaunchKernelGGL(sm_counts_kernel, dim3((unsigned)((n_counts + 255) / 256)), dim3(256), 0, s, (const uint32_t*)S.stats, n_counts, counts_dev);
+    ENG_HIP_CLEANUP(e, hipGetLastError());
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    cleanup();
+    return SABER_OK;
 }

@@ -564,6 +564,75 @@ class Engine:
         self._check(self.lib.saber_smooth_labels(self.h, _ptr(labels), labels.element_size(), Z, H, W, float(scale), _ptr(out), C.byref(n), _stream()))
         return out, n.value
 
+    # ------------------------------------------------------------------ smoothing over z-chunks (csrc/smooth3d.hip, segmenters/smooth.py)
+    _LABEL_DTYPES = (torch.uint8, torch.int16, torch.uint16, torch.int32, torch.uint32)
+
+    def _check_label_planes(self, who: str, name: str, t, hw=None, allow_empty: bool = False):
+        if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dim() != 3 or not t.is_contiguous()
+                or t.dtype not in self._LABEL_DTYPES or (t.shape[0] == 0 and not allow_empty) or t.shape[1] == 0 or t.shape[2] == 0):
+            raise ValueError(f"{who}: {name} must be a {'' if allow_empty else 'non-empty '}contiguous (Z,H,W) uint8 / (u)int16 / (u)int32 tensor on {self.device}")
+        if hw is not None and tuple(t.shape[1:]) != tuple(hw):
+            raise ValueError(f"{who}: {name} has planes of {tuple(t.shape[1:])}, the chunk's are {tuple(hw)}")
+
+    def smooth_radius(self, count: int, scale: float) -> int:
+        """The tap radius smooth_labels / smooth_labels_chunk use for a label of `count` voxels (the library's own arithmetic)."""
+        r = C.c_int(0)
+        if self.lib.saber_smooth_radius(int(count), float(scale), C.byref(r)) != _lib.SABER_OK:
+            raise ValueError(f"smooth_radius: count {count} must not be negative and scale {scale} must be positive")
+        return r.value
+
+    def label_max(self, labels: torch.Tensor) -> int:
+        """The largest label value of a (Z,H,W) uint8 / (u)int16 / (u)int32 device tensor (elements read as unsigned)."""
+        self._check_label_planes("label_max", "labels", labels)
+        m = C.c_uint32(0)
+        self._check(self.lib.saber_label_max(self.h, _ptr(labels), labels.element_size(), labels.numel(), C.byref(m), _stream()))
+        return m.value
+
+    def label_counts(self, labels: torch.Tensor, n: int) -> torch.Tensor:
+        """counts[v] = voxels of label value v for 0 < v < n, counts[0] = 0 (the background is not counted): an (n,) int64 device tensor.
+        Every value of `labels` must be below n."""
+        self._check_label_planes("label_counts", "labels", labels)
+        if not 1 <= int(n) <= (1 << 22) + 1:
+            raise ValueError(f"label_counts: a table of {n} entries (label values lie in [0, 2^22])")
+        out = torch.empty((int(n),), dtype=torch.int64, device=self.device)
+        Z, H, W = labels.shape
+        self._check(self.lib.saber_label_counts(self.h, _ptr(labels), labels.element_size(), Z, H, W, int(n), _ptr(out), _stream()))
+        return out
+
+    def smooth_labels_chunk(self, own: torch.Tensor, lo: Optional[torch.Tensor], hi: Optional[torch.Tensor], ids, counts, scale: float,
+                            lo_end: bool, hi_end: bool):
+        """smooth_labels on one z-chunk of a larger volume.  own: the chunk's (Zc,H,W) label planes; lo / hi: the planes right below / above
+        it (None or 0 planes: none), same dtype and H x W; ids, counts: the label values of the whole volume, ascending, and their voxel
+        counts there; lo_end / hi_end: the halo ends where the volume ends.  A halo must hold max(smooth_radius(count, scale)) planes unless
+        it is the volume's end.  Returns ((Zc,H,W) uint8 device tensor - bit for bit smooth_labels of the whole volume on these planes -
+        and the number of labels convolved)."""
+        who = "smooth_labels_chunk"
+        self._check_label_planes(who, "own", own)
+        Zc, H, W = own.shape
+        halos = []
+        for name, t in (("lo", lo), ("hi", hi)):
+            if t is not None:
+                self._check_label_planes(who, name, t, hw=(H, W), allow_empty=True)
+                if t.dtype != own.dtype:
+                    raise ValueError(f"{who}: {name} is {t.dtype}, own is {own.dtype}")
+            halos.append(t if t is not None and t.shape[0] else None)
+        lo, hi = halos
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1))
+        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int64)
+        if ids.size != counts.size:
+            raise ValueError(f"{who}: {ids.size} ids and {counts.size} counts")
+        if ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF):
+            raise ValueError(f"{who}: ids must be label values")
+        ids = ids.astype(np.uint32)
+        out = torch.empty((Zc, H, W), dtype=torch.uint8, device=self.device)
+        n = C.c_int(0)
+        self._check(self.lib.saber_smooth_labels_chunk(
+            self.h, _ptr(lo) if lo is not None else None, lo.shape[0] if lo is not None else 0, _ptr(own), Zc,
+            _ptr(hi) if hi is not None else None, hi.shape[0] if hi is not None else 0, int(bool(lo_end)), int(bool(hi_end)), own.element_size(),
+            H, W, ids.ctypes.data_as(C.c_void_p) if ids.size else None, counts.ctypes.data_as(C.c_void_p) if ids.size else None, int(ids.size),
+            float(scale), _ptr(out), C.byref(n), _stream()))
+        return out, n.value
+
     def gaussian_smoothing_3d(self, mask: torch.Tensor, sigma: float) -> torch.Tensor:
         """filters.gaussian.gaussian_smoothing_3d on the device.  mask: (Z,H,W) bool / uint8 0-1 device tensor -> float32 field."""
         assert mask.is_cuda and mask.dim() == 3 and mask.is_contiguous() and mask.dtype in (torch.bool, torch.uint8)

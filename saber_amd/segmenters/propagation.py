@@ -136,12 +136,13 @@ class propagationSegmenter(saber3D):
 
     @torch.inference_mode()
     def slice_by_slice_device(self, volume, text_prompt: str = None, stitch: bool = True, handles_per_gpu: int = 2,
-                              smooth_scale: float = None, sharded_stitch: bool = False):
+                              smooth_scale: float = None, sharded_stitch: bool = False, sharded_smooth: bool = False):
         """Same result as slice_by_slice, computed with device-resident masks and z-sharded over the ranks of the
         default torch.distributed process group (single process: all slices).  smooth_scale=0.05 appends the adaptive Gaussian
         smoothing segment_tomogram_core applies to the result (inference_core.py:68-74), still on the device (uint8 output).
         sharded_stitch: every rank labels its own z-chunk and the ranks exchange only what touches a seam (segment_volume_sharded); the
-        result is the same volume on every rank."""
+        result is the same volume on every rank.  sharded_smooth (with sharded_stitch and smooth_scale): every rank also smooths its own
+        chunk from a few halo planes of its neighbours (segmenters/smooth.py) and the ranks gather the uint8 chunks; the same bytes."""
         from saber_amd.adapters.sam2.automask import get_replica
         from saber_amd.segmenters.slice_driver import segment_slice_to_plane, segment_volume_sharded
         gen = self.adapter._generator()
@@ -177,5 +178,7 @@ class propagationSegmenter(saber3D):
             return one
 
         one = [make(e, c) for e, c in zip(engines, classifiers)]
+        if sharded_smooth and sharded_stitch and smooth_scale is not None:
+            return segment_volume_sharded(volume, one, stitch=stitch, engine=eng, sharded_stitch=True, sharded_smooth=smooth_scale)
         return segment_volume_sharded(volume, one, stitch=stitch, engine=eng, smooth_scale=smooth_scale,   # 3-D CC (+ smoothing) on the device
                                       sharded_stitch=sharded_stitch)

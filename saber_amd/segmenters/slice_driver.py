@@ -125,7 +125,7 @@ def shard_bounds(Z: int, world: int, rank: int) -> Tuple[int, int]:
 def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area: int = 100,
                            group=None, engine=None, smooth_scale: Optional[float] = None, timings: Optional[dict] = None,
                            keep_on_device: bool = False, planes_out: Optional[list] = None, sharded_stitch: bool = False,
-                           gather: str = "all") -> Optional[np.ndarray]:
+                           gather: str = "all", sharded_smooth: Optional[float] = None) -> Optional[np.ndarray]:
     """Slice-parallel slice_by_slice.  `volume` only supplies the shape (Z,H,W); `slice_fn(z)` returns the uint16
     label plane of slice z as a tensor on this rank's device.  All ranks receive every plane (all_gather of equal,
     zero-padded chunks); the (Z,H,W) uint32 stitched labels are returned (reference: utils.separate_masks).  With `engine`
@@ -145,7 +145,12 @@ def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area:
     `keep_on_device` the int32 device tensor); "rank0" - rank 0 returns it, the other ranks None; "none" - (this rank's chunk of labels,
     (z0, z1)): an int32 device tensor holding the uint32 labels for device planes, a uint32 array for CPU planes.  `smooth_scale` needs
     the whole volume: ValueError.  `timings` also receives `labelled` (chunk labelled, seam record ready) and `resolved` (seams resolved,
-    ids known); `stitched` is the relabelled chunk, `gathered` the arrival of the label chunks, `labels` the count of the whole volume."""
+    ids known); `stitched` is the relabelled chunk, `gathered` the arrival of the label chunks, `labels` the count of the whole volume.
+    `sharded_smooth` (a scale; only with `sharded_stitch`, `engine` and device planes, else ValueError): after the sharded stitch every
+    rank smooths its own chunk from the whole volume's label counts and a few halo planes of its neighbours (segmenters/smooth.py), byte
+    for byte what `smooth_scale` gives on the gathered volume.  `gather` then applies to the uint8 result, 1 B per voxel: "all" / "rank0"
+    return the (Z,H,W) uint8 array (with `keep_on_device` the device tensor), "none" (this rank's uint8 device chunk, (z0, z1)).
+    `timings` also receives `counted` (counts reduced, halo depth known), `halos` (halo planes arrived) and `smoothed`."""
     import time
     import torch.distributed as dist
     t_entry = time.perf_counter()
@@ -162,6 +167,8 @@ def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area:
             raise ValueError(f"segment_volume_sharded: gather must be 'all', 'rank0' or 'none', got {gather!r}")
         if smooth_scale is not None:
             raise ValueError("segment_volume_sharded: smooth_scale needs the whole volume on one rank; it cannot follow sharded_stitch")
+    if sharded_smooth is not None and (not sharded_stitch or engine is None):
+        raise ValueError("segment_volume_sharded: sharded_smooth needs sharded_stitch=True and an engine (the chunks are smoothed on the device)")
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
     rank = dist.get_rank(group) if dist_on else 0
@@ -218,6 +225,22 @@ def segment_volume_sharded(volume, slice_fn, stitch: bool = True, min_mask_area:
         stamp("stitched", dev)
         if timings is not None:
             timings["labels"] = n_labels
+        if sharded_smooth is not None:
+            from . import smooth as chunk_smooth
+            if not on_device and z1 > z0:
+                raise ValueError("segment_volume_sharded: sharded_smooth needs the planes on the engine's device: there is no CPU smoothing path")
+            if not on_device:                   # a rank without slices: it still takes part in the reductions
+                labels = torch.zeros((0, H, W), dtype=torch.int32, device=engine.device)
+            smoothed = chunk_smooth.smooth_rank(engine, labels, Z, H, W, bounds, rank, group, float(sharded_smooth),
+                                                stamp=lambda key: stamp(key, dev))
+            stamp("smoothed", dev)
+            if gather == "none":
+                return smoothed, (z0, z1)
+            full = chunk_smooth.gather_smoothed(smoothed, Z, H, W, bounds, rank, group, gather)
+            stamp("gathered", dev)
+            if full is None:
+                return None
+            return full if keep_on_device else full.cpu().numpy()
         if gather == "none":
             return labels, (z0, z1)
         full = chunked.gather_labels(labels, Z, H, W, bounds, rank, group, gather)
