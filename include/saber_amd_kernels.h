@@ -76,6 +76,14 @@ int saber_k_mask_post(const float* lowres, int n, int crop_x0, int crop_y0, int 
 int saber_k_mask_post_ex(const float* lowres, const int* idx, const uint8_t* pass, int n, int crop_x0, int crop_y0, int crop_w, int crop_h,
                          int H, int W, float thr, float offset, uint32_t* bits, int32_t* stats, void* stream);
 
+/* K8 for several crops in one launch (the crops of one decoded group of the mask generator).  A crop is 8 int32: box x0, y0, x1, y1, kbase,
+ * nm, and two words K8 does not read; its candidates are [kbase, kbase + nm), and every crop's kbase follows its predecessor's last candidate.
+ * crops_host and crops_dev hold the same n_crops records, in host and in device memory.  lowres / idx / pass / bits / stats are those of
+ * saber_k_mask_post_ex for the kbase[n_crops - 1] + nm[n_crops - 1] - kbase[0] candidates, candidate kbase[0] first.  The result is that of one
+ * saber_k_mask_post_ex call per crop. */
+int saber_k_mask_post_group(const float* lowres, const int* idx, const uint8_t* pass, const int32_t* crops_host, const int32_t* crops_dev, int n_crops,
+                            int H, int W, float thr, float offset, uint32_t* bits, int32_t* stats, void* stream);
+
 /* K1a: crop -> antialiased bilinear resize to res x res (ATen's tap rule) -> ImageNet normalisation.  img fp32 (H,W) for channels 1 / -1 or
  * (H,W,3) for channels 3; crops_dev: n x (x0, y0, x1, y1) int32 on the device; out [n][3][res][res].  channels -1: one grey plane that
  * already carries the model's normalisation (replicated, no statistics).  res must be a positive multiple of 16. */

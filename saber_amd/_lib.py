@@ -151,6 +151,7 @@ SIGNATURES = {
     "saber_k_prepare": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "saber_k_mask_post": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "saber_k_mask_post_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "saber_k_mask_post_group": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "saber_k_resize_normalize": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "saber_k_patch_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "saber_k_perm_index": (_i, [_i, _i, _i]),

@@ -305,7 +305,15 @@ extern "C" int saber_amg_generate(saber_engine* e, const float* img_dev, int H, 
         if (use_dev) {
             // K9a: IoU filter + plane index per group; K8 for every crop (filtered candidates exit at once); K9b / K10: filters, NMS, compaction per crop
             const float* iou_all = prm->use_m2m ? e->amg_iou2 : e->amg_iou1;
+            // the crop table first: K8 maps candidate -> crop through it, one launch per group
             std::vector<DevCrop> dcs;
+            for (const Grp& gr : groups)
+                for (int g = 0; g < gr.G; ++g) {
+                    const auto& box = crops[c0 + gr.ci + g];
+                    dcs.push_back(DevCrop{{box[0], box[1], box[2], box[3]}, (int)(gr.k0 + (size_t)g * gr.nm), gr.nm, (int)(gr.pt0 + (size_t)g * gr.np), M});
+                }
+            ENG_HIP(e, hipMemcpyAsync(e->amg_crops_dev, dcs.data(), sizeof(DevCrop) * dcs.size(), hipMemcpyHostToDevice, s));
+            size_t dc0 = 0;
             for (const Grp& gr : groups) {
                 ENG_KP(e, PC_ELEMENTWISE, 0.0, 0.0, launch_amg_plane(iou_all + gr.k0, gr.plane_mode == 2 ? e->amg_sel + gr.k0 : nullptr, gr.G * gr.nm, gr.plane_mode, prm->pred_iou_thresh,
                                                                   e->amg_idx + gr.k0, e->amg_pass + gr.k0, s));
@@ -314,16 +322,11 @@ extern "C" int saber_amg_generate(saber_engine* e, const float* img_dev, int H, 
                 if (lowres_clean)
                     ENG_KP(e, PC_MASK_POST, 0.0, 0.0, launch_clean_lowres(const_cast<float*>(gr.masks), e->amg_idx + gr.k0, e->amg_pass + gr.k0, gr.G * gr.nm, 256, 256, prm->mask_threshold,
                                                                          e->lowres_hole_area, e->lowres_sprinkle_area, s));
-                for (int g = 0; g < gr.G; ++g) {
-                    const auto& box = crops[c0 + gr.ci + g];
-                    DevCrop dc{{box[0], box[1], box[2], box[3]}, (int)(gr.k0 + (size_t)g * gr.nm), gr.nm, (int)(gr.pt0 + (size_t)g * gr.np), M};
-                    dcs.push_back(dc);
-                    ENG_KP(e, PC_MASK_POST, 0.0, (double)gr.nm * (65536.0 * 4 + (double)mask_words * 4),
-                           launch_mask_post(gr.masks, e->amg_idx + dc.kbase, gr.nm, box[0], box[1], box[2] - box[0], box[3] - box[1], H, W, prm->mask_threshold,
-                                            prm->stability_score_offset, e->amg_crop_bits + (slot_base + dc.kbase) * mask_words, e->amg_stats + dc.kbase, s, e->amg_pass + dc.kbase));
-                }
+                ENG_KP(e, PC_MASK_POST, 0.0, (double)gr.G * gr.nm * (65536.0 * 4 + (double)mask_words * 4),
+                       launch_mask_post_group(gr.masks, e->amg_idx + gr.k0, e->amg_crops_dev + dc0, dcs.data() + dc0, gr.G, H, W, prm->mask_threshold, prm->stability_score_offset,
+                                              e->amg_crop_bits + (slot_base + gr.k0) * mask_words, e->amg_stats + gr.k0, s, e->amg_pass + gr.k0));
+                dc0 += (size_t)gr.G;
             }
-            ENG_HIP(e, hipMemcpyAsync(e->amg_crops_dev, dcs.data(), sizeof(DevCrop) * dcs.size(), hipMemcpyHostToDevice, s));
             ENG_HIP(e, hipMemcpyAsync(e->amg_crop_pts, crop_pts_all.data(), sizeof(float) * 2 * n_pts, hipMemcpyHostToDevice, s));
             ENG_KP(e, PC_MASK_POST, 0.0, 0.0, launch_amg_crops(e->amg_crops_dev, (int)dcs.size(), max_nm, e->amg_stats, e->amg_pass, iou_all, e->amg_crop_pts, prm->stability_score_thresh,
                                                             prm->box_nms_thresh, H, W, (int)slot_base, e->amg_tmp, e->amg_keep, e->amg_counts, e->amg_surv, e->amg_nsurv, (int)total_cand, s));

@@ -149,6 +149,14 @@ extern "C" int saber_k_mask_post_ex(const float* lowres, const int* idx, const u
                                    reinterpret_cast<MaskStats*>(stats), (hipStream_t)stream, pass));
 }
 
+extern "C" int saber_k_mask_post_group(const float* lowres, const int* idx, const uint8_t* pass, const int32_t* crops_host, const int32_t* crops_dev, int n_crops,
+                                       int H, int W, float thr, float offset, uint32_t* bits, int32_t* stats, void* stream) {
+    static_assert(sizeof(DevCrop) == 8 * sizeof(int32_t), "saber_k_mask_post_group: 8 int32 per crop");
+    if (n_crops > 0 && (!crops_host || !crops_dev)) return kfail("mask_post_group: the crop table is needed on the host and on the device");
+    return kcheck(launch_mask_post_group(lowres, idx, reinterpret_cast<const DevCrop*>(crops_dev), reinterpret_cast<const DevCrop*>(crops_host), n_crops, H, W, thr, offset,
+                                         bits, reinterpret_cast<MaskStats*>(stats), (hipStream_t)stream, pass));
+}
+
 extern "C" int saber_k_resize_normalize(const float* img, int H, int W, int channels, const int* crops_dev, int n, float* out, int res, void* stream) {
     // the launcher's grid is res / 16 blocks per axis: any other res would leave a border of `out` unwritten
     if (res <= 0 || (res % 16) != 0) return kfail("resize_normalize: res must be a positive multiple of 16");

@@ -782,107 +782,166 @@ __global__ __launch_bounds__(256) void mask_post_kernel(const float* __restrict_
 // W <= 1024 (every SABER slice): the row loop with NO scalar work per 64-pixel chunk.  The previous form spent ~15 SALU instructions
 // per chunk (three popcounts, ffs / clz for the box, the bit-deposit bookkeeping) beside ~14 VALU; here
 //   * lane k keeps chunk k of the row's bits (v_writelane of the v_cmp result), so area / box come from ONE popcount / ffs / clz per
-//     lane and row instead of per chunk, and the row is stored as is;
+//     lane and row instead of per chunk;
 //   * the two stability counts are per-lane adds of the compare results, reduced across the wave once per 16 rows;
-//   * pixels outside the crop read a -3e38 sentinel (taps precomputed per block), the chunk loop skips chunks the crop does not touch;
-//   * vrow[256] repeats vrow[255], so the right tap is always x0 + 1 (one ds_read2).
+//   * pixels outside the crop read a -3e38 sentinel, the chunk loop skips chunks the crop does not touch;
+//   * vrow[256] repeats vrow[255], so the right tap is always x0 + 1 (one ds_read2);
+//   * the horizontal taps depend on the crop alone: the workgroup computes them once into LDS (same fp32 expressions as
+//     mask_post_kernel), each wave copies the chunks the crop touches into registers;
+//   * WIDE (rows a multiple of 16 bytes, 16-byte aligned bits): a wave's 16 rows are one contiguous piece of the bit plane.  Each row's
+//     words go to a wave-private LDS copy of that piece, which leaves as 16 bytes per lane (whole 128-byte lines at W32 = 32): 2 store
+//     instructions per wave where the row-by-row form issues 16-32.  Rows outside the crop take the same path with zeros; a wave or a
+//     workgroup whose rows the crop does not touch stores zeros and does nothing else.  !WIDE keeps one narrow store pair per row.
+//   * crops != nullptr (launch_mask_post_group): mask mi is candidate crops[0].kbase + mi and takes the box of the table entry that holds it.
 // Same arithmetic per pixel as mask_post_kernel: bit-identical masks and counts.
-__global__ __launch_bounds__(256) void mask_post_w1k_kernel(const float* __restrict__ lowres, const int* __restrict__ idx, int crop_x0,
-                                                            int crop_y0, int crop_w, int crop_h, int H, int W, float thr, float offset,
+template <bool WIDE>
+__global__ __launch_bounds__(256, 4) void mask_post_w1k_kernel(const float* __restrict__ lowres, const int* __restrict__ idx, const DevCrop* __restrict__ crops,
+                                                            int n_crops, int crop_x0, int crop_y0, int crop_w, int crop_h, int H, int W, float thr, float offset,
                                                             uint32_t* __restrict__ bits, MaskStats* __restrict__ stats, const uint8_t* __restrict__ pass) {
     if (pass && !pass[blockIdx.y]) return;
+    const int mi = blockIdx.y;
+    if (crops) {        // block-uniform
+        const int k = crops[0].kbase + mi;
+        int c = 0;
+        while (c < n_crops && (k < crops[c].kbase || k >= crops[c].kbase + crops[c].nm)) ++c;
+        if (c == n_crops) return;
+        crop_x0 = crops[c].box[0]; crop_y0 = crops[c].box[1]; crop_w = crops[c].box[2] - crop_x0; crop_h = crops[c].box[3] - crop_y0;
+    }
     __shared__ float vrow[4][260];
     __shared__ int red[4][8];
-    const int mi = blockIdx.y;
+    __shared__ int2 tap[1024];                                              // (x0, weight bits) of every column
+    __shared__ __attribute__((aligned(16))) uint32_t wbits[WIDE ? 4 : 1][WIDE ? 512 : 4];   // WIDE: the wave's 16 rows of bits, as they lie in memory
     const float* src = lowres + (int64_t)(idx ? idx[mi] : mi) * 65536;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int W32 = (W + 31) >> 5;
+    // workgroups are dealt to the 8 XCDs in launch order, so band b of EVERY mask would run on XCD b % 8, and a crop that covers
+    // only some bands would load only some XCDs: rotate the bands by the mask index
+    const int band = (int)((blockIdx.x + blockIdx.y) % gridDim.x);
+    const int ybase = band * MP_ROWS + wave * (MP_ROWS / 4);
+    // rows [y, y + nr) of this mask (all of them outside the crop) <- 0
+    auto zero_rows = [&](int y, int nr) {
+        if (WIDE) {
+            uint4* dst = reinterpret_cast<uint4*>(bits + ((int64_t)mi * H + y) * W32);
+            for (int q = lane; q < nr * (W32 >> 2); q += 64) dst[q] = make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            for (int r = 0; r < nr; ++r) {
+                uint32_t* brow = bits + ((int64_t)mi * H + y + r) * W32;
+                for (int wd = lane; wd < W32; wd += 64) brow[wd] = 0u;
+            }
+        }
+    };
+    const int wave_rows = min(MP_ROWS / 4, H - ybase);                     // <= 0: the wave has no row
+    if (band * MP_ROWS >= crop_y0 + crop_h || band * MP_ROWS + MP_ROWS <= crop_y0) {      // block-uniform: nothing to count
+        if (wave_rows > 0) zero_rows(ybase, wave_rows);
+        return;
+    }
     const float sy_scale = 256.0f / (float)crop_h, sx_scale = 256.0f / (float)crop_w;
     const int c_lo = max(crop_x0, 0) >> 6, c_hi = min(crop_x0 + crop_w - 1, W - 1) >> 6;
-    int x0a[16];
-    float lxa[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int x = 64 * c + lane, cx = x - crop_x0;
+    for (int x = 64 * c_lo + (int)threadIdx.x; x < 64 * c_hi + 64; x += 256) {
+        const int cx = x - crop_x0;
         float sx = ((float)cx + 0.5f) * sx_scale - 0.5f;
         sx = fmaxf(sx, 0.f);
         const int x0i = min((int)sx, 255);
         const bool valid = x < W && cx >= 0 && cx < crop_w;
-        x0a[c] = valid ? x0i : 257;
-        lxa[c] = valid ? sx - (float)x0i : 0.0f;
+        tap[x] = make_int2(valid ? x0i : 257, __float_as_int(valid ? sx - (float)x0i : 0.0f));
     }
     if (lane < 2) vrow[wave][257 + lane] = -3.0e38f;
-    auto fetch = [&](int y, float4* a, float4* b, float* ly) -> bool {
-        const int cy = y - crop_y0;
-        if (y >= H || cy < 0 || cy >= crop_h) return false;       // wave-uniform
-        float sy = ((float)cy + 0.5f) * sy_scale - 0.5f;
-        sy = fmaxf(sy, 0.f);
-        const int y0i = min((int)sy, 255), y1i = min(y0i + 1, 255);
-        *ly = sy - (float)y0i;
-        *a = *reinterpret_cast<const float4*>(src + y0i * 256 + lane * 4);
-        *b = *reinterpret_cast<const float4*>(src + y1i * 256 + lane * 4);
-        return true;
-    };
+    __syncthreads();
     int area = 0, inter = 0, uni = 0, xmin = 1 << 30, xmax = -1, ymin = 1 << 30, ymax = -1;     // per lane; y extents wave-uniform
-    const int ybase = blockIdx.x * MP_ROWS + wave * (MP_ROWS / 4);
-    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na;
-    float nly = 0.f;
-    bool nin = fetch(ybase, &na, &nb, &nly);
-    for (int r = 0; r < MP_ROWS / 4; ++r) {
-        const int y = ybase + r;
-        if (y >= H) break;  // wave-uniform
-        uint32_t* brow = bits + ((int64_t)mi * H + y) * W32;
-        const float4 a = na, b = nb;
-        const float ly = nly;
-        const bool in_crop = nin;
-        nin = (r + 1 < MP_ROWS / 4) ? fetch(y + 1, &na, &nb, &nly) : false;
-        if (!in_crop) {  // wave-uniform: rows outside the crop are all zero
-            for (int wd = lane; wd < W32; wd += 64) brow[wd] = 0u;
-            continue;
-        }
-        __builtin_amdgcn_wave_barrier();
-        {
-            float* vw = vrow[wave] + lane * 4;
-            vw[0] = (1.0f - ly) * a.x + ly * b.x; vw[1] = (1.0f - ly) * a.y + ly * b.y;
-            vw[2] = (1.0f - ly) * a.z + ly * b.z; vw[3] = (1.0f - ly) * a.w + ly * b.w;
-            if (lane == 63) vw[4] = vw[3];
-        }
-        __builtin_amdgcn_wave_barrier();
-        const float* vr = vrow[wave];
-        uint32_t blo = 0u, bhi = 0u;        // lane k: bits of pixels 64k .. 64k+63 of this row
-        // all taps of the row first (16 ds_read2 in flight, one wait; chunks outside the crop read the sentinel), then the chunks
-        float ta[16], tb[16];
+    if (wave_rows > 0 && (ybase >= crop_y0 + crop_h || ybase + MP_ROWS / 4 <= crop_y0)) {
+        zero_rows(ybase, wave_rows);                                        // wave-uniform: none of the wave's rows is in the crop
+    } else if (wave_rows > 0) {
+        int x0a[16];
+        float lxa[16];
 #pragma unroll
-        for (int cc = 0; cc < 16; ++cc) { ta[cc] = vr[x0a[cc]]; tb[cc] = vr[x0a[cc] + 1]; }
-        // one 64-pixel chunk; the lane select of v_writelane_b32 must be an inline constant (one SGPR per VALU instruction)
+        for (int c = 0; c < 16; ++c) {
+            x0a[c] = 257; lxa[c] = 0.0f;
+            if (c >= c_lo && c <= c_hi) { const int2 t = tap[64 * c + lane]; x0a[c] = t.x; lxa[c] = __int_as_float(t.y); }
+        }
+        auto fetch = [&](int y, float4* a, float4* b, float* ly) -> bool {
+            const int cy = y - crop_y0;
+            if (y >= H || cy < 0 || cy >= crop_h) return false;       // wave-uniform
+            float sy = ((float)cy + 0.5f) * sy_scale - 0.5f;
+            sy = fmaxf(sy, 0.f);
+            const int y0i = min((int)sy, 255), y1i = min(y0i + 1, 255);
+            *ly = sy - (float)y0i;
+            *a = *reinterpret_cast<const float4*>(src + y0i * 256 + lane * 4);
+            *b = *reinterpret_cast<const float4*>(src + y1i * 256 + lane * 4);
+            return true;
+        };
+        float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na;
+        float nly = 0.f;
+        bool nin = fetch(ybase, &na, &nb, &nly);
+#pragma unroll 1
+        for (int r = 0; r < MP_ROWS / 4; ++r) {
+            const int y = ybase + r;
+            if (y >= H) break;  // wave-uniform
+            uint32_t* brow = bits + ((int64_t)mi * H + y) * W32;
+            uint32_t* wrow = wbits[WIDE ? wave : 0] + (WIDE ? r * W32 : 0);                 // lanes 0 .. W32 / 2 - 1 write two words each
+            const float4 a = na, b = nb;
+            const float ly = nly;
+            const bool in_crop = nin;
+            nin = (r + 1 < MP_ROWS / 4) ? fetch(y + 1, &na, &nb, &nly) : false;
+            if (!in_crop) {  // wave-uniform: rows outside the crop are all zero
+                if (WIDE) { if (2 * lane < W32) *reinterpret_cast<uint2*>(wrow + 2 * lane) = make_uint2(0u, 0u); }
+                else for (int wd = lane; wd < W32; wd += 64) brow[wd] = 0u;
+                continue;
+            }
+            __builtin_amdgcn_wave_barrier();
+            {
+                float* vw = vrow[wave] + lane * 4;
+                vw[0] = (1.0f - ly) * a.x + ly * b.x; vw[1] = (1.0f - ly) * a.y + ly * b.y;
+                vw[2] = (1.0f - ly) * a.z + ly * b.z; vw[3] = (1.0f - ly) * a.w + ly * b.w;
+                if (lane == 63) vw[4] = vw[3];
+            }
+            __builtin_amdgcn_wave_barrier();
+            const float* vr = vrow[wave];
+            uint32_t blo = 0u, bhi = 0u;        // lane k: bits of pixels 64k .. 64k+63 of this row
+            // all taps of the row first (16 ds_read2 in flight, one wait; chunks outside the crop read the sentinel: a branch round each
+            // read pair makes sixteen waits of the one and measured 20-30 % slower), then the chunks
+            float ta[16], tb[16];
+#pragma unroll
+            for (int cc = 0; cc < 16; ++cc) { ta[cc] = vr[x0a[cc]]; tb[cc] = vr[x0a[cc] + 1]; }
+            // one 64-pixel chunk; the lane select of v_writelane_b32 must be an inline constant (one SGPR per VALU instruction)
 #define MP_CHUNK(cc)                                                                                              \
-        if ((cc) >= c_lo && (cc) <= c_hi) {                                                                       \
-            const float lx = lxa[cc];                                                                             \
-            const float v = (1.0f - lx) * ta[cc] + lx * tb[cc];                                                   \
-            const unsigned long long bm = __ballot(v > thr);                                                      \
-            asm("s_nop 1\n\tv_writelane_b32 %0, %1, " #cc : "+v"(blo) : "s"((uint32_t)bm));    /* VALU-written SGPR read by a VALU op: 2 wait states on gfx940+, and the hazard recogniser does not look inside asm */ \
-            asm("v_writelane_b32 %0, %1, " #cc : "+v"(bhi) : "s"((uint32_t)(bm >> 32)));                          \
-            inter += (v > thr + offset) ? 1 : 0;                                                                  \
-            uni += (v > thr - offset) ? 1 : 0;                                                                    \
-        }
-        MP_CHUNK(0) MP_CHUNK(1) MP_CHUNK(2) MP_CHUNK(3) MP_CHUNK(4) MP_CHUNK(5) MP_CHUNK(6) MP_CHUNK(7)
-        MP_CHUNK(8) MP_CHUNK(9) MP_CHUNK(10) MP_CHUNK(11) MP_CHUNK(12) MP_CHUNK(13) MP_CHUNK(14) MP_CHUNK(15)
+            if ((cc) >= c_lo && (cc) <= c_hi) {                                                                   \
+                const float lx = lxa[cc];                                                                         \
+                const float v = (1.0f - lx) * ta[cc] + lx * tb[cc];                                               \
+                const unsigned long long bm = __ballot(v > thr);                                                  \
+                asm("s_nop 1\n\tv_writelane_b32 %0, %1, " #cc : "+v"(blo) : "s"((uint32_t)bm));    /* VALU-written SGPR read by a VALU op: 2 wait states on gfx940+, and the hazard recogniser does not look inside asm */ \
+                asm("v_writelane_b32 %0, %1, " #cc : "+v"(bhi) : "s"((uint32_t)(bm >> 32)));                      \
+                inter += (v > thr + offset) ? 1 : 0;                                                              \
+                uni += (v > thr - offset) ? 1 : 0;                                                                \
+            }
+            MP_CHUNK(0) MP_CHUNK(1) MP_CHUNK(2) MP_CHUNK(3) MP_CHUNK(4) MP_CHUNK(5) MP_CHUNK(6) MP_CHUNK(7)
+            MP_CHUNK(8) MP_CHUNK(9) MP_CHUNK(10) MP_CHUNK(11) MP_CHUNK(12) MP_CHUNK(13) MP_CHUNK(14) MP_CHUNK(15)
 #undef MP_CHUNK
-        const int pc = __popc(blo) + __popc(bhi);
-        area += pc;
-        if (pc) {
-            xmin = min(xmin, lane * 64 + (blo ? __ffs((int)blo) - 1 : 31 + __ffs((int)bhi)));
-            xmax = max(xmax, lane * 64 + (bhi ? 63 - __clz((int)bhi) : 31 - __clz((int)blo)));
+            const int pc = __popc(blo) + __popc(bhi);
+            area += pc;
+            if (pc) {
+                xmin = min(xmin, lane * 64 + (blo ? __ffs((int)blo) - 1 : 31 + __ffs((int)bhi)));
+                xmax = max(xmax, lane * 64 + (bhi ? 63 - __clz((int)bhi) : 31 - __clz((int)blo)));
+            }
+            if (__ballot(pc != 0)) { ymin = min(ymin, y); ymax = max(ymax, y); }
+            if (WIDE) {
+                if (2 * lane < W32) *reinterpret_cast<uint2*>(wrow + 2 * lane) = make_uint2(blo, bhi);
+            } else {
+                const int wd = lane * 2;
+                if (wd < W32) brow[wd] = blo;
+                if (wd + 1 < W32) brow[wd + 1] = bhi;
+            }
         }
-        if (__ballot(pc != 0)) { ymin = min(ymin, y); ymax = max(ymax, y); }
-        const int wd = lane * 2;
-        if (wd < W32) brow[wd] = blo;
-        if (wd + 1 < W32) brow[wd + 1] = bhi;
-    }
+        if (WIDE) {     // the wave's rows, as they lie in LDS, to the bit plane: 16 bytes per lane
+            __builtin_amdgcn_wave_barrier();
+            uint4* dst = reinterpret_cast<uint4*>(bits + ((int64_t)mi * H + ybase) * W32);
+            const uint4* wsrc = reinterpret_cast<const uint4*>(wbits[WIDE ? wave : 0]);
+            for (int q = lane; q < wave_rows * (W32 >> 2); q += 64) dst[q] = wsrc[q];
+        }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        area += __shfl_xor(area, o, 64); inter += __shfl_xor(inter, o, 64); uni += __shfl_xor(uni, o, 64);
-        xmin = min(xmin, __shfl_xor(xmin, o, 64)); xmax = max(xmax, __shfl_xor(xmax, o, 64));
+        for (int o = 32; o > 0; o >>= 1) {
+            area += __shfl_xor(area, o, 64); inter += __shfl_xor(inter, o, 64); uni += __shfl_xor(uni, o, 64);
+            xmin = min(xmin, __shfl_xor(xmin, o, 64)); xmax = max(xmax, __shfl_xor(xmax, o, 64));
+        }
     }
     if (lane == 0) {
         red[wave][0] = area; red[wave][1] = inter; red[wave][2] = uni; red[wave][3] = xmin;
@@ -911,15 +970,53 @@ __global__ void mask_stats_init_kernel(MaskStats* stats, int n) {
     if (i < n) { MaskStats s; s.area = 0; s.inter = 0; s.uni = 0; s.x0 = 1 << 30; s.y0 = 1 << 30; s.x1 = -1; s.y1 = -1; s.pad = 0; stats[i] = s; }
 }
 
+// the W <= 1024 kernel: full-line stores where every row of bits is a whole number of 16-byte pieces at a 16-byte aligned address
+static void mask_post_w1k(const float* lowres, const int* idx, const DevCrop* crops, int n_crops, int n, int crop_x0, int crop_y0, int crop_w, int crop_h, int H, int W,
+                          float thr, float offset, uint32_t* bits, MaskStats* stats, hipStream_t s, const uint8_t* pass) {
+    const dim3 grid((H + MP_ROWS - 1) / MP_ROWS, n);
+    const bool wide = (((W + 31) >> 5) & 3) == 0 && (reinterpret_cast<uintptr_t>(bits) & 15) == 0;
+    if (wide) hipLaunchKernelGGL(mask_post_w1k_kernel<true>, grid, dim3(256), 0, s, lowres, idx, crops, n_crops, crop_x0, crop_y0, crop_w, crop_h, H, W, thr, offset, bits, stats, pass);
+    else hipLaunchKernelGGL(mask_post_w1k_kernel<false>, grid, dim3(256), 0, s, lowres, idx, crops, n_crops, crop_x0, crop_y0, crop_w, crop_h, H, W, thr, offset, bits, stats, pass);
+}
+
 const char* launch_mask_post(const float* lowres, const int* idx, int n, int crop_x0, int crop_y0, int crop_w, int crop_h, int H,
                              int W, float thr, float offset, uint32_t* bits, MaskStats* stats, hipStream_t s, const uint8_t* pass) {
     if (n <= 0) return nullptr;
     if (crop_w <= 0 || crop_h <= 0) return "mask_post: empty crop";
     hipLaunchKernelGGL(mask_stats_init_kernel, dim3((n + 255) / 256), dim3(256), 0, s, stats, n);
     const dim3 grid((H + MP_ROWS - 1) / MP_ROWS, n);
-    if (W <= 1024 && !(g_saber_debug_flags & 8)) hipLaunchKernelGGL(mask_post_w1k_kernel, grid, dim3(256), 0, s, lowres, idx, crop_x0, crop_y0, crop_w, crop_h, H, W, thr, offset, bits, stats, pass);
+    if (W <= 1024 && !(g_saber_debug_flags & 8)) mask_post_w1k(lowres, idx, nullptr, 0, n, crop_x0, crop_y0, crop_w, crop_h, H, W, thr, offset, bits, stats, s, pass);
     else if (W <= 1024) hipLaunchKernelGGL(mask_post_kernel<true>, grid, dim3(256), 0, s, lowres, idx, crop_x0, crop_y0, crop_w, crop_h, H, W, thr, offset, bits, stats, pass);
     else hipLaunchKernelGGL(mask_post_kernel<false>, grid, dim3(256), 0, s, lowres, idx, crop_x0, crop_y0, crop_w, crop_h, H, W, thr, offset, bits, stats, pass);
+    return nullptr;
+}
+
+// K8 for the crops of one decoded group in ONE launch (and one initialisation of the statistics).  crops_host[0 .. n_crops): the crops in
+// candidate order, each the candidates [kbase, kbase + nm) that follow its predecessor's; crops_dev: the same records on the device.
+// idx / bits / stats / pass (and lowres when idx is null) start at candidate crops_host[0].kbase.  W > 1024, debug flag 8 (the reference
+// kernel) and debug flag 131072 (A/B of the launch count) go through launch_mask_post crop by crop.
+const char* launch_mask_post_group(const float* lowres, const int* idx, const DevCrop* crops_dev, const DevCrop* crops_host, int n_crops, int H, int W, float thr,
+                                   float offset, uint32_t* bits, MaskStats* stats, hipStream_t s, const uint8_t* pass) {
+    if (n_crops <= 0) return nullptr;
+    int n = 0;
+    for (int c = 0; c < n_crops; ++c) {
+        const DevCrop& dc = crops_host[c];
+        if (dc.nm <= 0 || dc.kbase != crops_host[0].kbase + n) return "mask_post_group: the crops' candidates are not consecutive";
+        if (dc.box[2] <= dc.box[0] || dc.box[3] <= dc.box[1]) return "mask_post: empty crop";
+        n += dc.nm;
+    }
+    if (W > 1024 || (g_saber_debug_flags & (8 | 131072))) {
+        const int64_t words = (int64_t)H * ((W + 31) >> 5);
+        for (int c = 0; c < n_crops; ++c) {
+            const DevCrop& dc = crops_host[c];
+            const int off = dc.kbase - crops_host[0].kbase;
+            if (const char* m = launch_mask_post(idx ? lowres : lowres + (int64_t)off * 65536, idx ? idx + off : nullptr, dc.nm, dc.box[0], dc.box[1], dc.box[2] - dc.box[0],
+                                                 dc.box[3] - dc.box[1], H, W, thr, offset, bits + off * words, stats + off, s, pass ? pass + off : nullptr)) return m;
+        }
+        return nullptr;
+    }
+    hipLaunchKernelGGL(mask_stats_init_kernel, dim3((n + 255) / 256), dim3(256), 0, s, stats, n);
+    mask_post_w1k(lowres, idx, crops_dev, n_crops, n, 0, 0, 0, 0, H, W, thr, offset, bits, stats, s, pass);
     return nullptr;
 }
 

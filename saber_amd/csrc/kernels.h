@@ -244,7 +244,7 @@ SABER_OP_FWD(launch_prompt_tokens) SABER_OP_FWD(launch_prompt_tokens_multi) SABE
 SABER_OP_FWD(launch_dec_attention) SABER_OP_FWD(launch_mask_pick) SABER_OP_FWD(launch_iou_live_flags) SABER_OP_FWD(launch_mask_select)
 SABER_OP_FWD(launch_dec_t2i) SABER_OP_FWD(launch_dec_i2t) SABER_OP_FWD(launch_dec_upscale) SABER_OP_FWD(launch_hyper_pack) SABER_OP_FWD(launch_dec_tokens)
 SABER_OP_FWD(launch_prompt_tokens16) SABER_OP_FWD(launch_dec_tokens16) SABER_OP_FWD(launch_dec_i2t16)
-SABER_OP_FWD(launch_mask_post) SABER_OP_FWD(launch_gather_masks) SABER_OP_FWD(launch_label_plane) SABER_OP_FWD(launch_pair_intersections) SABER_OP_FWD(launch_unpermute_nchw)
+SABER_OP_FWD(launch_mask_post) SABER_OP_FWD(launch_mask_post_group) SABER_OP_FWD(launch_gather_masks) SABER_OP_FWD(launch_label_plane) SABER_OP_FWD(launch_pair_intersections) SABER_OP_FWD(launch_unpermute_nchw)
 SABER_OP_FWD(launch_rope) SABER_OP_FWD(launch_softmax_rows) SABER_OP_FWD(launch_conv3x3s2) SABER_OP_FWD(launch_unpack_masks) SABER_OP_FWD(launch_paint_nearest)
 SABER_OP_FWD(launch_conv3x3s2_t) SABER_OP_FWD(launch_dwconv7_t) SABER_OP_FWD(launch_dwconv7) SABER_OP_FWD(launch_conv4x4s4) SABER_OP_FWD(launch_resize_plane)
 SABER_OP_FWD(launch_resize_planes_non_overlap)

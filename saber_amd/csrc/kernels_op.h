@@ -86,6 +86,10 @@ const char* launch_dec_i2t16(const bf16_t* X, XMap xm, const bf16_t* peq, const 
 const char* decoder_t16_init_device();
 const char* launch_mask_post(const float* lowres, const int* idx, int n, int crop_x0, int crop_y0, int crop_w, int crop_h, int H,
                              int W, float thr, float offset, uint32_t* bits, MaskStats* stats, hipStream_t s, const uint8_t* pass = nullptr);   // pass: optional per-mask flags, masks with 0 are skipped
+// the same for the crops of one decoded group in one launch: crops_host / crops_dev hold the same n_crops records (box, kbase, nm) in candidate
+// order; idx / bits / stats / pass (lowres when idx is null) start at candidate crops_host[0].kbase
+const char* launch_mask_post_group(const float* lowres, const int* idx, const DevCrop* crops_dev, const DevCrop* crops_host, int n_crops, int H, int W, float thr,
+                                   float offset, uint32_t* bits, MaskStats* stats, hipStream_t s, const uint8_t* pass = nullptr);
 // paint label planes: plane[y][x] = max over i (in order) ... later masks overwrite earlier ones (propagation.py:185-186)
 const char* launch_gather_masks(const uint32_t* src, const int* idx, uint32_t* dst, int n, int64_t words, hipStream_t s);
 const char* launch_label_plane(const uint32_t* bits, const int* order, int n, int H, int W, uint16_t* plane, hipStream_t s);
