@@ -176,10 +176,16 @@ void prof_end(saber_engine* e, hipStream_t s);
 
 int eng_fail(saber_engine* e, int code, const std::string& msg);
 void refine_release(saber_engine* e);       // morph3d.hip: frees refine_state
-// smooth3d.hip: largest label value (atomicMax into *out) and stats[v] = {count, zmin, ymin, xmin, zmax, ymax, xmax, -} of a (Z,H,W)
-// label volume of 1-, 2- or 4-byte unsigned elements; with zflag only the planes z whose zflag[z] is set count.  They only enqueue.
-void label_max(const void* lab, int elem_bytes, const uint8_t* zflag_or_null, int64_t plane, int64_t n, uint32_t* out, hipStream_t s);
-void label_stats(const void* lab, int elem_bytes, const uint8_t* zflag_or_null, int Z, int H, int W, uint32_t* stats, hipStream_t s);
+// smooth3d.hip: label volumes of 1-, 2- or 4-byte unsigned elements that lie in n_bufs (<= 3) buffers; a buffer of 0 voxels / planes is
+// passed over.  With zflag (one buffer, `plane` voxels per plane) only the planes z whose zflag[z] is set count.  Both allocate and
+// free their device scratch, return on the host and synchronise s once.
+// *out_max = the largest label value of the buffers (n[b] voxels each)
+hipError_t label_max_host(const void* const* bufs, const int64_t* n, int n_bufs, int elem_bytes, const uint8_t* zflag_or_null, int64_t plane,
+                          uint32_t* out_max, hipStream_t s);
+// st[(b * n_stats + v) * 8 ...] = {count, zmin, ymin, xmin, zmax, ymax, xmax, -} of label value v < n_stats in buffer b (planes[b] planes
+// of H x W, z local to the buffer); a value that is absent keeps {0, ~0, ~0, ~0, 0, 0, 0, 0}.  n_stats must exceed the largest label value.
+hipError_t label_stats_host(const void* const* bufs, const int* planes, int n_bufs, int elem_bytes, const uint8_t* zflag_or_null, int H, int W,
+                            size_t n_stats, std::vector<uint32_t>& st, hipStream_t s);
 // blocks of 256 threads for n elements of a grid-stride kernel: at least one, at most cap
 inline unsigned eng_blocks(int64_t n, int64_t cap = 1 << 16) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, cap)); }
 // h[0..2]: the sentinel counters as read from the device; SABER_OK or SABER_ERR_RANGE with a message that names the stage

@@ -17,7 +17,7 @@
 //                         then (z,y-1,x) and (z-1,y,x) in cc6_merge.  Two consumers, both without a host round trip: "zero the
 //                         components below min_size" and "keep the largest, the first in raster order on ties" (one 64-bit atomicMax
 //                         over the roots of size << 32 | ~root).
-//   label_max / _stats    largest label, voxel count + bounding box per organelle label on the planes that hold membrane (smooth3d.hip)
+//   label_max_host / label_stats_host   largest label, voxel count + bounding box per organelle label on the planes that hold membrane (smooth3d.hip)
 //   small kernels         edge trim, per-z membrane presence, byte OR / AND, population count, the 3x3x3 organelle boundary of the
 //                         surface test (inside cc6_overlap), scatter into the two label maps, expansion of stored pairs into planes.
 // Host synchronisations of one saber_refine_membranes call: 3 (largest label; per-label statistics; per-organelle flags at the end),
@@ -463,11 +463,11 @@ extern "C" int saber_components6_3d(saber_engine* e, const uint8_t* mask_dev, in
 namespace {
 struct RfScratch {
     uint8_t *trim = nullptr, *clean = nullptr, *zflag = nullptr, *b_org = nullptr, *b_cl = nullptr, *b_comb = nullptr, *b_t = nullptr;
-    uint32_t *maxv = nullptr, *stats = nullptr, *flags = nullptr, *p_org = nullptr, *p_mem = nullptr, *p_a = nullptr, *p_b = nullptr, *p_c = nullptr;
+    uint32_t *flags = nullptr, *p_org = nullptr, *p_mem = nullptr, *p_a = nullptr, *p_b = nullptr, *p_c = nullptr;
     CcWs cc;
     void release() {
         (void)hipFree(trim); (void)hipFree(clean); (void)hipFree(zflag); (void)hipFree(b_org); (void)hipFree(b_cl); (void)hipFree(b_comb); (void)hipFree(b_t);
-        (void)hipFree(maxv); (void)hipFree(stats); (void)hipFree(flags); (void)hipFree(p_org); (void)hipFree(p_mem); (void)hipFree(p_a); (void)hipFree(p_b);
+        (void)hipFree(flags); (void)hipFree(p_org); (void)hipFree(p_mem); (void)hipFree(p_a); (void)hipFree(p_b);
         (void)hipFree(p_c); (void)hipFree(cc.lab); (void)hipFree(cc.sizes); (void)hipFree(cc.ov); (void)hipFree(cc.best);
     }
 };
@@ -498,7 +498,6 @@ int refine_run(saber_engine* e, const T* org, const uint8_t* mem, int Z, int H, 
     ENG_HIP_CLEANUP(e, hipMalloc(&R.cc.lab, (size_t)n * 4));
     ENG_HIP_CLEANUP(e, hipMalloc(&R.cc.sizes, (size_t)n * 4));
     ENG_HIP_CLEANUP(e, hipMalloc(&R.cc.best, 8));
-    ENG_HIP_CLEANUP(e, hipMalloc(&R.maxv, 4));
     const int tz = P->edge_trim_z, txy = P->edge_trim_xy;
     int z0 = 0, z1 = 0, y0 = 0, y1 = 0, x0 = 0, x1 = 0;        // empty boxes unless the trims are usable
     if (tz > 0 && tz < Z / 2) { z0 = tz; z1 = Z - tz; }
@@ -510,11 +509,9 @@ int refine_run(saber_engine* e, const T* org, const uint8_t* mem, int Z, int H, 
     hipLaunchKernelGGL(mo_zpresence_kernel, dim3((unsigned)std::min<int64_t>((plane + 255) / 256, 64), Z), dim3(256), 0, s, (const uint8_t*)R.clean, plane,
                        R.zflag);
     // ---- step 3 (:478-480): the labels present, with voxel count and bounding box
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(R.maxv, 0, 4, s));
-    label_max(org, sizeof(T), R.zflag, plane, n, R.maxv, s);
+    const void* org_buf = org;
     uint32_t maxv = 0;
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, R.maxv, 4, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                        // synchronisation 1
+    ENG_HIP_CLEANUP(e, label_max_host(&org_buf, &n, 1, sizeof(T), R.zflag, plane, &maxv, s));      // synchronisation 1
     if (maxv == 0) { cleanup(); return SABER_OK; }
     if (maxv > MO_MAX_LABEL) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "refine_membranes: label values above 2^22 are not supported"); }
     const uint64_t type_max = sizeof(T) == 1 ? 0xffull : (sizeof(T) == 2 ? 0xffffull : 0xffffffffull);
@@ -524,14 +521,8 @@ int refine_run(saber_engine* e, const T* org, const uint8_t* mem, int Z, int H, 
                                                   " does not fit the label type (the reference would wrap silently)");
     }
     const size_t n_stats = (size_t)maxv + 1;
-    std::vector<uint32_t> st(n_stats * 8);
-    for (size_t v = 0; v < n_stats; ++v) { uint32_t* p = &st[v * 8]; p[0] = 0; p[1] = p[2] = p[3] = 0xffffffffu; p[4] = p[5] = p[6] = p[7] = 0; }
-    ENG_HIP_CLEANUP(e, hipMalloc(&R.stats, n_stats * 32));
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(R.stats, st.data(), n_stats * 32, hipMemcpyHostToDevice, s));
-    label_stats(org, sizeof(T), R.zflag, Z, H, W, R.stats, s);
-    ENG_HIP_CLEANUP(e, hipGetLastError());
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(st.data(), R.stats, n_stats * 32, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                        // synchronisation 2
+    std::vector<uint32_t> st;
+    ENG_HIP_CLEANUP(e, label_stats_host(&org_buf, &Z, 1, sizeof(T), R.zflag, H, W, n_stats, st, s));      // synchronisation 2
     // ---- host: ROI per label (_get_organelle_roi, :251-272) and the shape-dependent radii (:364-374)
     std::vector<RfCand> cands;
     const int pad = P->ball_size / 2;

@@ -11,16 +11,21 @@
 // field cannot pass the threshold there; and along an axis that has been convolved the other two still see zeros outside the box.
 //   1. sm_max / sm_stats   largest label value; voxel count + bounding box per label value (one atomic set per wave and label)
 //   2. host                sigma, radius, taps per present label (double / float arithmetic as the reference's numpy / torch lines)
-//   3. sm_conv_x           T1 = conv_x(volume == v) on the box, all labels of a group in one launch
+//   3. sm_conv_x           T1 = conv_x(volume == v) on the box, all labels of a group in one launch; rows come through a segment table
 //   4. sm_conv_axis<0>     T2 = conv_y(T1)
-//   5. sm_conv_axis<1>     field = conv_z(T2); field > 0.5 -> atomicMax(winner, v)   ("later label overwrites" = largest label)
+//   5. sm_conv_axis<1>     field = conv_z(T2) on the box's own planes; field > 0.5 -> atomicMax(winner, v)   ("later label overwrites" =
+//                          largest label)
 //   6. sm_cast             out = (uint8) winner  (the reference's result array is uint8: label values wrap modulo 256)
 // HBM-bound byte work: ~20 B per box voxel.  Each output sums its taps in ascending tap order with fma, as the CPU oracle does.
+// Steps 3-6 are sm_convolve, the one pipeline behind every entry point.
 //
-// One z-chunk of a volume that is spread over several ranks (saber_smooth_labels_chunk, at the end of this file): the same steps on
-// (planes below, own planes, planes above) in three buffers, with the counts of the whole volume handed in - sm_conv_x_seg reads its
-// rows through a segment table, sm_conv_z_own writes the winner of the own planes only.
+// One z-chunk of a volume that is spread over several ranks (saber_smooth_labels_chunk, at the end of this file): steps 1-2 on (planes
+// below, own planes, planes above) in three buffers, with the counts of the whole volume handed in, then the same sm_convolve: the
+// segment table names the three buffers, a box's own planes are those of the chunk, and the winner covers the own planes only.  The
+// whole volume (sm_run) is the chunk without halos: one segment, every box written on all its planes, output plane 0 = volume plane 0.
+// So both routes sum every output with the same instructions.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -105,115 +110,20 @@ __device__ __forceinline__ int sm_find(const int* __restrict__ prefix, int n, in
     return lo;
 }
 
-// T1[z][y][x] = sum_k taps[k] * (vol[z0+z][y0+y][x0+x+k-r] == label), x+k-r inside the box.  4 waves = 4 rows of the box, 64 x each.
-template <typename T>
-__global__ __launch_bounds__(256) void sm_conv_x_kernel(const T* __restrict__ vol, int H, int W, const SmLabel* __restrict__ labels,
-                                                        const int* __restrict__ prefix, int n_labels, const float* __restrict__ taps,
-                                                        float* __restrict__ ws) {
-    extern __shared__ float sm_lds[];
-    const int li = sm_find(prefix, n_labels, blockIdx.x);
-    const SmLabel L = labels[li];
-    const int t = blockIdx.x - prefix[li];
-    const int xchunks = (L.dx + 63) / 64;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row = (t / xchunks) * 4 + wave;                   // row of the box: z * dy + y
-    const int xc = (t % xchunks) * 64;
-    const int seg = 64 + 2 * L.r;
-    float* s = sm_lds + wave * seg;
-    const bool live = row < L.dz * L.dy;
-    if (live) {
-        const int z = row / L.dy, y = row % L.dy;
-        const T* p = vol + ((int64_t)(L.z0 + z) * H + (L.y0 + y)) * W + L.x0;
-        for (int i = lane; i < seg; i += 64) {
-            const int x = xc - L.r + i;
-            s[i] = (x >= 0 && x < L.dx && (uint32_t)p[x] == L.label) ? 1.0f : 0.0f;
-        }
-    }
-    __syncthreads();
-    if (!live || xc + lane >= L.dx) return;
-    const float* tp = taps + L.tap_off;
-    float acc = 0.0f;
-    for (int k = 0; k <= 2 * L.r; ++k) acc = fmaf(tp[k], s[lane + k], acc);
-    ws[L.ws_off + (int64_t)row * L.dx + xc + lane] = acc;
-}
-
-// 1-D convolution along y (AXIS 0: T1 -> T2) or z (AXIS 1: T2 -> field -> threshold / dense float output).
-// Block = SM_TL outputs along the axis x SM_TX columns of one (outer) plane; thread = one column, SM_OPT consecutive outputs.
-template <int AXIS, bool FLOAT_OUT>
-__global__ __launch_bounds__(256) void sm_conv_axis_kernel(const SmLabel* __restrict__ labels, const int* __restrict__ prefix, int n_labels,
-                                                           const float* __restrict__ taps, float* __restrict__ ws, int H, int W,
-                                                           uint32_t* __restrict__ winner, float* __restrict__ dense) {
-    extern __shared__ float sm_lds[];
-    const int li = sm_find(prefix, n_labels, blockIdx.x);
-    const SmLabel L = labels[li];
-    int t = blockIdx.x - prefix[li];
-    const int len = AXIS == 0 ? L.dy : L.dz;                    // convolved axis
-    const int n_outer = AXIS == 0 ? L.dz : L.dy;
-    const int64_t st_axis = AXIS == 0 ? L.dx : (int64_t)L.dy * L.dx;
-    const int64_t st_outer = AXIS == 0 ? (int64_t)L.dy * L.dx : L.dx;
-    const int xchunks = (L.dx + SM_TX - 1) / SM_TX, lchunks = (len + SM_TL - 1) / SM_TL;
-    const int xc = (t % xchunks) * SM_TX; t /= xchunks;
-    const int l0 = (t % lchunks) * SM_TL;
-    const int outer = t / lchunks;
-    (void)n_outer;
-    const int64_t vol = (int64_t)L.dz * L.dy * L.dx;
-    const float* src = ws + L.ws_off + (AXIS == 0 ? 0 : vol) + outer * st_outer;
-    const int rows = SM_TL + 2 * L.r;
-    const int xl = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    const bool xok = xc + xl < L.dx;
-    for (int j = grp; j < rows; j += 4) {
-        const int l = l0 - L.r + j;
-        sm_lds[j * SM_TX + xl] = (xok && l >= 0 && l < len) ? src[l * st_axis + xc + xl] : 0.0f;
-    }
-    __syncthreads();
-    const int o0 = grp * SM_OPT;                                // this thread's outputs l0 + o0 .. + SM_OPT-1
-    if (!xok || l0 + o0 >= len) return;
-    // input j (relative to l0 + o0 - r) feeds output o with tap j - o; the tap table has SM_OPT-1 zeros on both sides
-    const float* tp = taps + L.tap_off;
-    float acc[SM_OPT];
-#pragma unroll
-    for (int o = 0; o < SM_OPT; ++o) acc[o] = 0.0f;
-    const float* col = sm_lds + o0 * SM_TX + xl;
-    for (int j = 0; j < 2 * L.r + SM_OPT; ++j) {
-        const float v = col[j * SM_TX];
-#pragma unroll
-        for (int o = 0; o < SM_OPT; ++o) acc[o] = fmaf(tp[j - o], v, acc[o]);
-    }
-#pragma unroll
-    for (int o = 0; o < SM_OPT; ++o) {
-        const int l = l0 + o0 + o;
-        if (l >= len) break;
-        if (AXIS == 0) {
-            ws[L.ws_off + vol + outer * st_outer + l * st_axis + xc + xl] = acc[o];
-        } else {
-            const int64_t g = ((int64_t)(L.z0 + l) * H + (L.y0 + outer)) * W + L.x0 + xc + xl;
-            if (FLOAT_OUT) dense[g] = acc[o];
-            else if (acc[o] > 0.5f) atomicMax(winner + g, L.label);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void sm_cast_kernel(const uint32_t* __restrict__ winner, uint8_t* __restrict__ out, int64_t n) {
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        const uint4 w = reinterpret_cast<const uint4*>(winner)[i];
-        reinterpret_cast<uint32_t*>(out)[i] = (w.x & 255u) | ((w.y & 255u) << 8) | ((w.z & 255u) << 16) | (w.w << 24);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[(n4 << 2) + threadIdx.x] = (uint8_t)winner[(n4 << 2) + threadIdx.x];
-}
-
-// ---- one z-chunk of a volume (saber_smooth_labels_chunk): the planes below, the own planes and the planes above lie in three buffers.
-// Planes are counted from the first plane of the lower halo; plane p lies in the last segment whose first[] <= p.
+// The planes of a volume in up to three buffers (saber_smooth_labels_chunk: the planes below, the own planes, the planes above).  Planes
+// are counted from the first plane of the first buffer; plane p lies in the last segment whose first[] <= p.  A whole volume is one
+// segment: first = {0, INT_MAX, INT_MAX}.
 struct SmSegs {
     const void* base[3];
     int first[3];
 };
 
-// sm_conv_x_kernel with the rows read through the segment table
+// T1[z][y][x] = sum_k taps[k] * (vol[z0+z][y0+y][x0+x+k-r] == label), x+k-r inside the box.  4 waves = 4 rows of the box, 64 x each.
+// The row pointer comes from the segment table (two wave-uniform selects).
 template <typename T>
-__global__ __launch_bounds__(256) void sm_conv_x_seg_kernel(SmSegs segs, int H, int W, const SmLabel* __restrict__ labels,
-                                                            const int* __restrict__ prefix, int n_labels, const float* __restrict__ taps,
-                                                            float* __restrict__ ws) {
+__global__ __launch_bounds__(256) void sm_conv_x_kernel(SmSegs segs, int H, int W, const SmLabel* __restrict__ labels,
+                                                        const int* __restrict__ prefix, int n_labels, const float* __restrict__ taps,
+                                                        float* __restrict__ ws) {
     extern __shared__ float sm_lds[];
     const int li = sm_find(prefix, n_labels, blockIdx.x);
     const SmLabel L = labels[li];
@@ -244,33 +154,41 @@ __global__ __launch_bounds__(256) void sm_conv_x_seg_kernel(SmSegs segs, int H, 
     ws[L.ws_off + (int64_t)row * L.dx + xc + lane] = acc;
 }
 
-// sm_conv_axis_kernel<1, false> for the own planes of the box only: own[li] = {the box's first own plane (box-local), how many};
-// `winner` holds the own planes, own0 = the first of them in segment planes.  The sum of an output is that kernel's: taps ascending, fma.
-__global__ __launch_bounds__(256) void sm_conv_z_own_kernel(const SmLabel* __restrict__ labels, const int* __restrict__ prefix, int n_labels,
-                                                            const int2* __restrict__ own, const float* __restrict__ taps,
-                                                            const float* __restrict__ ws, int H, int W, int own0, uint32_t* __restrict__ winner) {
+// 1-D convolution along y (AXIS 0: T1 -> T2) or z (AXIS 1: T2 -> field -> threshold / dense float output).
+// Block = SM_TL outputs along the axis x SM_TX columns of one (outer) plane; thread = one column, SM_OPT consecutive outputs.
+// AXIS 1 writes the planes own[li] = {first (box-local), how many} of the box only, into an output whose plane 0 is the volume's plane
+// own0: a z-chunk's own planes, or {0, dz} and 0 for a whole volume.  The inputs are the box's planes [0, dz) whatever is written.
+template <int AXIS, bool FLOAT_OUT>
+__global__ __launch_bounds__(256) void sm_conv_axis_kernel(const SmLabel* __restrict__ labels, const int* __restrict__ prefix, int n_labels,
+                                                           const int2* __restrict__ own, int own0, const float* __restrict__ taps,
+                                                           float* __restrict__ ws, int H, int W, uint32_t* __restrict__ winner,
+                                                           float* __restrict__ dense) {
     extern __shared__ float sm_lds[];
     const int li = sm_find(prefix, n_labels, blockIdx.x);
     const SmLabel L = labels[li];
-    const int2 O = own[li];
     int t = blockIdx.x - prefix[li];
-    const int64_t st_axis = (int64_t)L.dy * L.dx;
-    const int xchunks = (L.dx + SM_TX - 1) / SM_TX, lchunks = (O.y + SM_TL - 1) / SM_TL;
+    const int len = AXIS == 0 ? L.dy : L.dz;                    // convolved axis: inputs [0, len)
+    int lbeg = 0, lend = len;                                   // outputs [lbeg, lend)
+    if (AXIS == 1) { const int2 O = own[li]; lbeg = O.x; lend = O.x + O.y; }
+    const int64_t st_axis = AXIS == 0 ? L.dx : (int64_t)L.dy * L.dx;
+    const int64_t st_outer = AXIS == 0 ? (int64_t)L.dy * L.dx : L.dx;
+    const int xchunks = (L.dx + SM_TX - 1) / SM_TX, lchunks = (lend - lbeg + SM_TL - 1) / SM_TL;
     const int xc = (t % xchunks) * SM_TX; t /= xchunks;
-    const int l0 = O.x + (t % lchunks) * SM_TL;
-    const int y = t / lchunks;
-    const int lend = O.x + O.y;
-    const float* src = ws + L.ws_off + (int64_t)L.dz * st_axis + (int64_t)y * L.dx;
+    const int l0 = lbeg + (t % lchunks) * SM_TL;
+    const int outer = t / lchunks;
+    const int64_t vol = (int64_t)L.dz * L.dy * L.dx;
+    const float* src = ws + L.ws_off + (AXIS == 0 ? 0 : vol) + outer * st_outer;
     const int rows = SM_TL + 2 * L.r;
     const int xl = threadIdx.x & 63, grp = threadIdx.x >> 6;
     const bool xok = xc + xl < L.dx;
     for (int j = grp; j < rows; j += 4) {
         const int l = l0 - L.r + j;
-        sm_lds[j * SM_TX + xl] = (xok && l >= 0 && l < L.dz) ? src[l * st_axis + xc + xl] : 0.0f;
+        sm_lds[j * SM_TX + xl] = (xok && l >= 0 && l < len) ? src[l * st_axis + xc + xl] : 0.0f;
     }
     __syncthreads();
-    const int o0 = grp * SM_OPT;
+    const int o0 = grp * SM_OPT;                                // this thread's outputs l0 + o0 .. + SM_OPT-1
     if (!xok || l0 + o0 >= lend) return;
+    // input j (relative to l0 + o0 - r) feeds output o with tap j - o; the tap table has SM_OPT-1 zeros on both sides
     const float* tp = taps + L.tap_off;
     float acc[SM_OPT];
 #pragma unroll
@@ -285,9 +203,23 @@ __global__ __launch_bounds__(256) void sm_conv_z_own_kernel(const SmLabel* __res
     for (int o = 0; o < SM_OPT; ++o) {
         const int l = l0 + o0 + o;
         if (l >= lend) break;
-        const int64_t g = ((int64_t)(L.z0 + l - own0) * H + (L.y0 + y)) * W + L.x0 + xc + xl;
-        if (acc[o] > 0.5f) atomicMax(winner + g, L.label);
+        if (AXIS == 0) {
+            ws[L.ws_off + vol + outer * st_outer + l * st_axis + xc + xl] = acc[o];
+        } else {
+            const int64_t g = ((int64_t)(L.z0 + l - own0) * H + (L.y0 + outer)) * W + L.x0 + xc + xl;
+            if (FLOAT_OUT) dense[g] = acc[o];
+            else if (acc[o] > 0.5f) atomicMax(winner + g, L.label);
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void sm_cast_kernel(const uint32_t* __restrict__ winner, uint8_t* __restrict__ out, int64_t n) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const uint4 w = reinterpret_cast<const uint4*>(winner)[i];
+        reinterpret_cast<uint32_t*>(out)[i] = (w.x & 255u) | ((w.y & 255u) << 8) | ((w.z & 255u) << 16) | (w.w << 24);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[(n4 << 2) + threadIdx.x] = (uint8_t)winner[(n4 << 2) + threadIdx.x];
 }
 
 // counts[v] = stats[v].count as int64 (saber_label_counts)
@@ -323,87 +255,198 @@ static int sm_make_taps(double sigma, std::vector<float>& out) {
 
 namespace {
 struct SmScratch {
-    uint32_t *maxv = nullptr, *stats = nullptr, *winner = nullptr;
+    uint32_t* winner = nullptr;
     SmLabel* labels = nullptr;
+    int2* own = nullptr;
     int* prefix = nullptr;
     float *taps = nullptr, *ws = nullptr;
-    int2* own = nullptr;                    // saber_smooth_labels_chunk only
     void release() {
-        (void)hipFree(maxv); (void)hipFree(stats); (void)hipFree(winner); (void)hipFree(labels); (void)hipFree(prefix); (void)hipFree(taps); (void)hipFree(ws);
-        (void)hipFree(own);
+        (void)hipFree(winner); (void)hipFree(labels); (void)hipFree(own); (void)hipFree(prefix); (void)hipFree(taps); (void)hipFree(ws);
     }
 };
 
-template <typename T>
-void sm_launch_conv_x(const T* vol, int H, int W, const SmLabel* labels, const int* prefix, int n, int tiles, int rmax, const float* taps,
-                      float* ws, hipStream_t s) {
-    hipLaunchKernelGGL(sm_conv_x_kernel<T>, dim3(tiles), dim3(256), (size_t)4 * (64 + 2 * rmax) * sizeof(float), s, vol, H, W, labels, prefix,
-                       n, taps, ws);
+// f(T()) with T the unsigned type of elem_bytes (1, 2 or 4) bytes
+template <typename F>
+void sm_by_elem(int elem_bytes, F&& f) {
+    if (elem_bytes == 1) f(uint8_t());
+    else if (elem_bytes == 2) f(uint16_t());
+    else f(uint32_t());
 }
 
-template <typename T>
-void sm_launch_max(const T* lab, const uint8_t* zflag, int64_t plane, int64_t n, uint32_t* out, hipStream_t s) {
-    if (zflag) hipLaunchKernelGGL((sm_max_kernel<T, true>), dim3(eng_blocks(n)), dim3(256), 0, s, lab, zflag, plane, n, out);
-    else hipLaunchKernelGGL((sm_max_kernel<T, false>), dim3(eng_blocks(n)), dim3(256), 0, s, lab, zflag, plane, n, out);
+// largest label value (atomicMax into *out) and stats[v] of a label volume; with zflag only the planes z whose zflag[z] is set count.
+// They only enqueue.
+void sm_launch_max(const void* lab, int elem_bytes, const uint8_t* zflag, int64_t plane, int64_t n, uint32_t* out, hipStream_t s) {
+    sm_by_elem(elem_bytes, [&](auto t) {
+        using T = decltype(t);
+        if (zflag) hipLaunchKernelGGL((sm_max_kernel<T, true>), dim3(eng_blocks(n)), dim3(256), 0, s, (const T*)lab, zflag, plane, n, out);
+        else hipLaunchKernelGGL((sm_max_kernel<T, false>), dim3(eng_blocks(n)), dim3(256), 0, s, (const T*)lab, zflag, plane, n, out);
+    });
 }
-template <typename T>
-void sm_launch_stats(const T* lab, const uint8_t* zflag, int Z, int H, int W, uint32_t* stats, hipStream_t s) {
+void sm_launch_stats(const void* lab, int elem_bytes, const uint8_t* zflag, int Z, int H, int W, uint32_t* stats, hipStream_t s) {
     const int64_t rows = (int64_t)Z * H;
     const unsigned grid = (unsigned)((rows * ((W + 511) / 512) + 3) / 4);
-    if (zflag) hipLaunchKernelGGL((sm_stats_kernel<T, true>), dim3(grid), dim3(256), 0, s, lab, zflag, W, rows, H, stats);
-    else hipLaunchKernelGGL((sm_stats_kernel<T, false>), dim3(grid), dim3(256), 0, s, lab, zflag, W, rows, H, stats);
+    sm_by_elem(elem_bytes, [&](auto t) {
+        using T = decltype(t);
+        if (zflag) hipLaunchKernelGGL((sm_stats_kernel<T, true>), dim3(grid), dim3(256), 0, s, (const T*)lab, zflag, W, rows, H, stats);
+        else hipLaunchKernelGGL((sm_stats_kernel<T, false>), dim3(grid), dim3(256), 0, s, (const T*)lab, zflag, W, rows, H, stats);
+    });
 }
 }  // namespace
 
-void label_max(const void* lab, int elem_bytes, const uint8_t* zflag, int64_t plane, int64_t n, uint32_t* out, hipStream_t s) {
-    if (elem_bytes == 1) sm_launch_max((const uint8_t*)lab, zflag, plane, n, out, s);
-    else if (elem_bytes == 2) sm_launch_max((const uint16_t*)lab, zflag, plane, n, out, s);
-    else sm_launch_max((const uint32_t*)lab, zflag, plane, n, out, s);
+hipError_t label_max_host(const void* const* bufs, const int64_t* n, int n_bufs, int elem_bytes, const uint8_t* zflag, int64_t plane,
+                          uint32_t* out_max, hipStream_t s) {
+    uint32_t* dev = nullptr;
+    hipError_t st = hipMalloc(&dev, 4);
+    if (st == hipSuccess) st = hipMemsetAsync(dev, 0, 4, s);
+    if (st == hipSuccess) {
+        for (int b = 0; b < n_bufs; ++b)
+            if (n[b]) sm_launch_max(bufs[b], elem_bytes, zflag, plane, n[b], dev, s);
+        st = hipGetLastError();
+    }
+    if (st == hipSuccess) st = hipMemcpyAsync(out_max, dev, 4, hipMemcpyDeviceToHost, s);
+    if (st == hipSuccess) st = hipStreamSynchronize(s);
+    (void)hipFree(dev);
+    return st;
 }
 
-void label_stats(const void* lab, int elem_bytes, const uint8_t* zflag, int Z, int H, int W, uint32_t* stats, hipStream_t s) {
-    if (elem_bytes == 1) sm_launch_stats((const uint8_t*)lab, zflag, Z, H, W, stats, s);
-    else if (elem_bytes == 2) sm_launch_stats((const uint16_t*)lab, zflag, Z, H, W, stats, s);
-    else sm_launch_stats((const uint32_t*)lab, zflag, Z, H, W, stats, s);
+hipError_t label_stats_host(const void* const* bufs, const int* planes, int n_bufs, int elem_bytes, const uint8_t* zflag, int H, int W,
+                            size_t n_stats, std::vector<uint32_t>& st, hipStream_t s) {
+    const size_t rows = (size_t)n_bufs * n_stats;
+    st.resize(rows * 8);
+    for (size_t v = 0; v < rows; ++v) { uint32_t* p = &st[v * 8]; p[0] = 0; p[1] = p[2] = p[3] = 0xffffffffu; p[4] = p[5] = p[6] = p[7] = 0; }
+    uint32_t* dev = nullptr;
+    hipError_t err = hipMalloc(&dev, rows * 32);
+    if (err == hipSuccess) err = hipMemcpyAsync(dev, st.data(), rows * 32, hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) {
+        for (int b = 0; b < n_bufs; ++b)
+            if (planes[b]) sm_launch_stats(bufs[b], elem_bytes, zflag, planes[b], H, W, dev + (size_t)b * n_stats * 8, s);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(st.data(), dev, rows * 32, hipMemcpyDeviceToHost, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    (void)hipFree(dev);
+    return err;
 }
 
-// mode 0: label volume -> uint8 (fast_3d_gaussian_smoothing);  mode 1: binary mask (any non-zero) + fixed sigma -> float field
+// Steps 3-6 for the labels of `labs` (ascending label value; their ws_off is set here): the volume's planes are read through `segs`,
+// label i writes the planes owns[i] of its box, and plane own0 of the volume is plane 0 of the output - the uint8 label volume out_u8 of
+// n_out voxels (through a winner volume of its own), or the dense float field of the one label.  Labels run in groups whose two fp32
+// boxes fit the workspace (>= the largest single label, at least 1 GiB of floats when useful); one host synchronisation per group.
+static int sm_convolve(saber_engine* e, const char* who, const SmSegs& segs, int elem_bytes, int H, int W, std::vector<SmLabel>& labs,
+                       const std::vector<int2>& owns, int own0, const std::vector<float>& taps, uint8_t* out_u8, int64_t n_out, float* out_dense,
+                       hipStream_t s) {
+    SmScratch S;
+    auto cleanup = [&]() { S.release(); };
+    if (labs.empty()) { ENG_HIP(e, hipStreamSynchronize(s)); return SABER_OK; }
+    int64_t total = 0, biggest = 0;
+    for (auto& L : labs) {
+        const int64_t v = (int64_t)L.dz * L.dy * L.dx;
+        total += 2 * v;
+        biggest = std::max(biggest, v);
+    }
+    const int64_t ws_floats = std::min(total, std::max<int64_t>(2 * biggest, (int64_t)1 << 28));
+    const size_t stride = labs.size() + 1;
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.ws, (size_t)ws_floats * 4));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.taps, taps.size() * 4));
+    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.labels, labs.size() * sizeof(SmLabel)));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.own, labs.size() * sizeof(int2)));
+    ENG_HIP_CLEANUP(e, hipMalloc(&S.prefix, 3 * stride * sizeof(int)));
+    if (out_u8) {
+        ENG_HIP_CLEANUP(e, hipMalloc(&S.winner, (size_t)n_out * 4));
+        ENG_HIP_CLEANUP(e, hipMemsetAsync(S.winner, 0, (size_t)n_out * 4, s));
+    }
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
+    std::vector<int> prefix;
+    size_t g0 = 0;
+    while (g0 < labs.size()) {
+        size_t g1 = g0;
+        int64_t used = 0;
+        int grmax = 0;
+        int64_t tiles[3] = {0, 0, 0};
+        prefix.assign(3 * stride, 0);
+        while (g1 < labs.size()) {
+            SmLabel& L = labs[g1];
+            const int64_t v2 = 2 * (int64_t)L.dz * L.dy * L.dx;
+            if (g1 > g0 && used + v2 > ws_floats) break;
+            const int64_t xch = (L.dx + 63) / 64;
+            const int64_t tx = (((int64_t)L.dz * L.dy + 3) / 4) * xch;
+            const int64_t ty = (int64_t)L.dz * ((L.dy + SM_TL - 1) / SM_TL) * xch;
+            const int64_t tz = (int64_t)L.dy * ((owns[g1].y + SM_TL - 1) / SM_TL) * xch;
+            if (tiles[0] + tx > 0x7fffffff || tiles[1] + ty > 0x7fffffff || tiles[2] + tz > 0x7fffffff) {
+                if (g1 == g0) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, std::string(who) + ": label too large"); }
+                break;
+            }
+            L.ws_off = used;
+            used += v2;
+            grmax = std::max(grmax, L.r);
+            const size_t i = g1 - g0;
+            prefix[0 * stride + i] = (int)tiles[0]; prefix[1 * stride + i] = (int)tiles[1]; prefix[2 * stride + i] = (int)tiles[2];
+            tiles[0] += tx; tiles[1] += ty; tiles[2] += tz;
+            ++g1;
+        }
+        const int ng = (int)(g1 - g0);
+        for (int a = 0; a < 3; ++a) prefix[a * stride + ng] = (int)tiles[a];
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.labels, labs.data() + g0, (size_t)ng * sizeof(SmLabel), hipMemcpyHostToDevice, s));
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.own, owns.data() + g0, (size_t)ng * sizeof(int2), hipMemcpyHostToDevice, s));
+        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.prefix, prefix.data(), prefix.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        sm_by_elem(elem_bytes, [&](auto t) {
+            hipLaunchKernelGGL(sm_conv_x_kernel<decltype(t)>, dim3((unsigned)tiles[0]), dim3(256), (size_t)4 * (64 + 2 * grmax) * sizeof(float), s, segs,
+                               H, W, (const SmLabel*)S.labels, (const int*)S.prefix, ng, (const float*)S.taps, S.ws);
+        });
+        const size_t lds = (size_t)(SM_TL + 2 * grmax) * SM_TX * sizeof(float);
+        hipLaunchKernelGGL((sm_conv_axis_kernel<0, false>), dim3((unsigned)tiles[1]), dim3(256), lds, s, (const SmLabel*)S.labels,
+                           (const int*)(S.prefix + stride), ng, (const int2*)S.own, own0, (const float*)S.taps, S.ws, H, W, (uint32_t*)nullptr,
+                           (float*)nullptr);
+        if (out_u8)
+            hipLaunchKernelGGL((sm_conv_axis_kernel<1, false>), dim3((unsigned)tiles[2]), dim3(256), lds, s, (const SmLabel*)S.labels,
+                               (const int*)(S.prefix + 2 * stride), ng, (const int2*)S.own, own0, (const float*)S.taps, S.ws, H, W, S.winner,
+                               (float*)nullptr);
+        else
+            hipLaunchKernelGGL((sm_conv_axis_kernel<1, true>), dim3((unsigned)tiles[2]), dim3(256), lds, s, (const SmLabel*)S.labels,
+                               (const int*)(S.prefix + 2 * stride), ng, (const int2*)S.own, own0, (const float*)S.taps, S.ws, H, W,
+                               (uint32_t*)nullptr, out_dense);
+        ENG_HIP_CLEANUP(e, hipGetLastError());
+        ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                    // the descriptor / prefix host buffers are reused by the next group
+        g0 = g1;
+    }
+    if (out_u8) {
+        hipLaunchKernelGGL(sm_cast_kernel, dim3((unsigned)std::min<int64_t>((n_out / 4 + 255) / 256 + 1, 1 << 16)), dim3(256), 0, s,
+                           (const uint32_t*)S.winner, out_u8, n_out);
+        ENG_HIP_CLEANUP(e, hipGetLastError());
+    }
+    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    cleanup();
+    return SABER_OK;
+}
+
+// mode 0: label volume -> uint8 (fast_3d_gaussian_smoothing);  mode 1: binary mask (any non-zero) + fixed sigma -> float field.
+// The whole volume is the chunk without halos whose own planes are all of them: one segment, every box written on [0, dz), own0 = 0.
 static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, int H, int W, double scale, double fixed_sigma, int mode,
                   void* out_dev, int* out_n_labels, hipStream_t s) {
     const int64_t n = (int64_t)Z * H * W;
-    SmScratch S;
-    auto cleanup = [&]() { S.release(); };
     ENG_DEVICE(e);
     if (out_n_labels) *out_n_labels = 0;
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
-    label_max(vol_dev, elem_bytes, nullptr, 0, n, S.maxv, s);
     uint32_t maxv = 0;
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, S.maxv, 4, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
-    if (mode == 0) ENG_HIP_CLEANUP(e, hipMemsetAsync(out_dev, 0, (size_t)n, s));
-    else ENG_HIP_CLEANUP(e, hipMemsetAsync(out_dev, 0, (size_t)n * 4, s));
-    if (maxv == 0) { ENG_HIP_CLEANUP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
-    if (maxv > SM_MAX_LABEL) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "smooth_labels: label values above 2^22 are not supported"); }
+    ENG_HIP(e, label_max_host(&vol_dev, &n, 1, elem_bytes, nullptr, 0, &maxv, s));
+    ENG_HIP(e, hipMemsetAsync(out_dev, 0, (size_t)n * (mode == 0 ? 1 : 4), s));
+    if (maxv == 0) { ENG_HIP(e, hipStreamSynchronize(s)); return SABER_OK; }
+    if (maxv > SM_MAX_LABEL) return eng_fail(e, SABER_ERR_INVALID, "smooth_labels: label values above 2^22 are not supported");
     // ---- per-label count + bounding box
     const size_t n_stats = (size_t)maxv + 1;
-    std::vector<uint32_t> st(n_stats * 8);
-    for (size_t v = 0; v < n_stats; ++v) { uint32_t* p = &st[v * 8]; p[0] = 0; p[1] = p[2] = p[3] = 0xffffffffu; p[4] = p[5] = p[6] = p[7] = 0; }
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.stats, n_stats * 32));
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.stats, st.data(), n_stats * 32, hipMemcpyHostToDevice, s));
-    label_stats(vol_dev, elem_bytes, nullptr, Z, H, W, S.stats, s);
-    ENG_HIP_CLEANUP(e, hipGetLastError());
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(st.data(), S.stats, n_stats * 32, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    std::vector<uint32_t> st;
+    ENG_HIP(e, label_stats_host(&vol_dev, &Z, 1, elem_bytes, nullptr, H, W, n_stats, st, s));
     // ---- host: sigma, radius, taps per present label, ascending label value (np.unique order, masks.py:253-262)
     std::vector<SmLabel> labs;
+    std::vector<int2> owns;
     std::vector<float> taps(SM_OPT - 1, 0.0f);
     int rmax = 0;
-    int64_t biggest = 0;
     for (size_t v = 1; v < n_stats; ++v) {
         const uint32_t* p = &st[v * 8];
         if (!p[0]) continue;
-        if (mode == 1 && v != 1) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "gaussian_smoothing_3d: the input must be a 0/1 mask"); }
+        if (mode == 1 && v != 1) return eng_fail(e, SABER_ERR_INVALID, "gaussian_smoothing_3d: the input must be a 0/1 mask");
         SmLabel L;
         L.label = (uint32_t)v;
         L.z0 = (int)p[1]; L.y0 = (int)p[2]; L.x0 = (int)p[3];
@@ -416,84 +459,15 @@ static int sm_run(saber_engine* e, const void* vol_dev, int elem_bytes, int Z, i
         taps.insert(taps.end(), SM_OPT - 1, 0.0f);
         L.ws_off = 0;
         rmax = std::max(rmax, L.r);
-        biggest = std::max(biggest, (int64_t)L.dz * L.dy * L.dx);
         labs.push_back(L);
+        owns.push_back(make_int2(0, L.dz));
     }
-    if ((size_t)(SM_TL + 2 * rmax) * SM_TX * sizeof(float) > SM_LDS_LIMIT) {
-        cleanup();
+    if ((size_t)(SM_TL + 2 * rmax) * SM_TX * sizeof(float) > SM_LDS_LIMIT)
         return eng_fail(e, SABER_ERR_INVALID, "smooth_labels: Gaussian radius " + std::to_string(rmax) + " exceeds the supported 284 voxels");
-    }
     if (out_n_labels) *out_n_labels = (int)labs.size();
-    // ---- groups of labels whose two fp32 boxes fit the workspace (>= the largest single label, at least 1 GiB of floats when useful)
-    int64_t total = 0;
-    for (auto& L : labs) total += 2 * (int64_t)L.dz * L.dy * L.dx;
-    const int64_t ws_floats = std::min(total, std::max<int64_t>(2 * biggest, (int64_t)1 << 28));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.ws, (size_t)ws_floats * 4));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.taps, taps.size() * 4));
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.labels, labs.size() * sizeof(SmLabel)));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.prefix, 3 * (labs.size() + 1) * sizeof(int)));
-    if (mode == 0) {
-        ENG_HIP_CLEANUP(e, hipMalloc(&S.winner, (size_t)n * 4));
-        ENG_HIP_CLEANUP(e, hipMemsetAsync(S.winner, 0, (size_t)n * 4, s));
-    }
-    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
-    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
-    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
-    std::vector<int> prefix;
-    size_t g0 = 0;
-    while (g0 < labs.size()) {
-        size_t g1 = g0;
-        int64_t used = 0;
-        int grmax = 0;
-        int64_t tiles[3] = {0, 0, 0};
-        prefix.assign(3 * (labs.size() + 1), 0);
-        const size_t stride = labs.size() + 1;
-        while (g1 < labs.size()) {
-            SmLabel& L = labs[g1];
-            const int64_t v2 = 2 * (int64_t)L.dz * L.dy * L.dx;
-            if (g1 > g0 && used + v2 > ws_floats) break;
-            L.ws_off = used;
-            used += v2;
-            grmax = std::max(grmax, L.r);
-            const int64_t xch = (L.dx + 63) / 64;
-            const int64_t tx = (((int64_t)L.dz * L.dy + 3) / 4) * xch;
-            const int64_t ty = (int64_t)L.dz * ((L.dy + SM_TL - 1) / SM_TL) * xch;
-            const int64_t tz = (int64_t)L.dy * ((L.dz + SM_TL - 1) / SM_TL) * xch;
-            if (tiles[0] + tx > 0x7fffffff || tiles[1] + ty > 0x7fffffff || tiles[2] + tz > 0x7fffffff) { if (g1 == g0) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "smooth_labels: label too large"); } break; }
-            const size_t i = g1 - g0;
-            prefix[0 * stride + i] = (int)tiles[0]; prefix[1 * stride + i] = (int)tiles[1]; prefix[2 * stride + i] = (int)tiles[2];
-            tiles[0] += tx; tiles[1] += ty; tiles[2] += tz;
-            ++g1;
-        }
-        const int ng = (int)(g1 - g0);
-        for (int a = 0; a < 3; ++a) prefix[a * stride + ng] = (int)tiles[a];
-        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.labels, labs.data() + g0, (size_t)ng * sizeof(SmLabel), hipMemcpyHostToDevice, s));
-        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.prefix, prefix.data(), prefix.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        if (elem_bytes == 1) sm_launch_conv_x((const uint8_t*)vol_dev, H, W, S.labels, S.prefix, ng, (int)tiles[0], grmax, S.taps + 0, S.ws, s);
-        else if (elem_bytes == 2) sm_launch_conv_x((const uint16_t*)vol_dev, H, W, S.labels, S.prefix, ng, (int)tiles[0], grmax, S.taps + 0, S.ws, s);
-        else sm_launch_conv_x((const uint32_t*)vol_dev, H, W, S.labels, S.prefix, ng, (int)tiles[0], grmax, S.taps + 0, S.ws, s);
-        const size_t lds = (size_t)(SM_TL + 2 * grmax) * SM_TX * sizeof(float);
-        hipLaunchKernelGGL((sm_conv_axis_kernel<0, false>), dim3((unsigned)tiles[1]), dim3(256), lds, s, (const SmLabel*)S.labels,
-                           (const int*)(S.prefix + stride), ng, (const float*)S.taps, S.ws, H, W, (uint32_t*)nullptr, (float*)nullptr);
-        if (mode == 0)
-            hipLaunchKernelGGL((sm_conv_axis_kernel<1, false>), dim3((unsigned)tiles[2]), dim3(256), lds, s, (const SmLabel*)S.labels,
-                               (const int*)(S.prefix + 2 * stride), ng, (const float*)S.taps, S.ws, H, W, S.winner, (float*)nullptr);
-        else
-            hipLaunchKernelGGL((sm_conv_axis_kernel<1, true>), dim3((unsigned)tiles[2]), dim3(256), lds, s, (const SmLabel*)S.labels,
-                               (const int*)(S.prefix + 2 * stride), ng, (const float*)S.taps, S.ws, H, W, (uint32_t*)nullptr, (float*)out_dev);
-        ENG_HIP_CLEANUP(e, hipGetLastError());
-        ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                    // the descriptor / prefix host buffers are reused by the next group
-        g0 = g1;
-    }
-    if (mode == 0) {
-        hipLaunchKernelGGL(sm_cast_kernel, dim3((unsigned)std::min<int64_t>((n / 4 + 255) / 256 + 1, 1 << 16)), dim3(256), 0, s,
-                           (const uint32_t*)S.winner, (uint8_t*)out_dev, n);
-        ENG_HIP_CLEANUP(e, hipGetLastError());
-    }
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
-    cleanup();
-    return SABER_OK;
+    const SmSegs segs = {{vol_dev, vol_dev, vol_dev}, {0, INT_MAX, INT_MAX}};
+    return sm_convolve(e, "smooth_labels", segs, elem_bytes, H, W, labs, owns, 0, taps, mode == 0 ? (uint8_t*)out_dev : nullptr, n,
+                       mode == 0 ? nullptr : (float*)out_dev, s);
 }
 
 extern "C" int saber_smooth_labels(saber_engine* e, const void* labels_dev, int elem_bytes, int Z, int H, int W, double scale,
@@ -555,48 +529,32 @@ extern "C" int saber_smooth_labels_chunk(saber_engine* e, const void* lo_dev, in
     if ((lo_planes < rtab && !lo_is_volume_end) || (hi_planes < rtab && !hi_is_volume_end))
         return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: a halo of " + std::to_string(lo_planes < rtab && !lo_is_volume_end ? lo_planes : hi_planes) +
                                                   " planes is shorter than the largest radius " + std::to_string(rtab) + " and is not the volume's end");
-    SmScratch S;
-    auto cleanup = [&]() { S.release(); };
     ENG_DEVICE(e);
     if (out_n_labels) *out_n_labels = 0;
     const void* bufs[3] = {lo_dev, own_dev, hi_dev};
     const int planes[3] = {lo_planes, own_planes, hi_planes};
+    const int64_t voxels[3] = {lo_planes * plane, n_own, hi_planes * plane};
     const int first[3] = {0, own0, own1};
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
-    for (int b = 0; b < 3; ++b)
-        if (planes[b]) label_max(bufs[b], elem_bytes, nullptr, 0, planes[b] * plane, S.maxv, s);
     uint32_t maxv = 0;
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, S.maxv, 4, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(out_dev, 0, (size_t)n_own, s));
-    if (maxv == 0) { ENG_HIP_CLEANUP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
-    if (maxv > SM_MAX_LABEL) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: label values above 2^22 are not supported"); }
+    ENG_HIP(e, label_max_host(bufs, voxels, 3, elem_bytes, nullptr, 0, &maxv, s));
+    ENG_HIP(e, hipMemsetAsync(out_dev, 0, (size_t)n_own, s));
+    if (maxv == 0) { ENG_HIP(e, hipStreamSynchronize(s)); return SABER_OK; }
+    if (maxv > SM_MAX_LABEL) return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: label values above 2^22 are not supported");
     // ---- count + bounding box per label value and buffer (z local to the buffer)
     const size_t n_stats = (size_t)maxv + 1;
-    std::vector<uint32_t> st(3 * n_stats * 8);
-    for (size_t v = 0; v < 3 * n_stats; ++v) { uint32_t* p = &st[v * 8]; p[0] = 0; p[1] = p[2] = p[3] = 0xffffffffu; p[4] = p[5] = p[6] = p[7] = 0; }
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.stats, 3 * n_stats * 32));
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.stats, st.data(), 3 * n_stats * 32, hipMemcpyHostToDevice, s));
-    for (int b = 0; b < 3; ++b)
-        if (planes[b]) label_stats(bufs[b], elem_bytes, nullptr, planes[b], H, W, S.stats + (size_t)b * n_stats * 8, s);
-    ENG_HIP_CLEANUP(e, hipGetLastError());
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(st.data(), S.stats, 3 * n_stats * 32, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
+    std::vector<uint32_t> st;
+    ENG_HIP(e, label_stats_host(bufs, planes, 3, elem_bytes, nullptr, H, W, n_stats, st, s));
     // ---- host: per label value the box inside [own0 - r, own1 + r) and its own planes, ascending label value
     std::vector<SmLabel> labs;
     std::vector<int2> owns;
     std::vector<float> taps(SM_OPT - 1, 0.0f);
-    int64_t biggest = 0;
     int ti = 0;
     for (size_t v = 1; v < n_stats; ++v) {
         const uint32_t* q[3] = {&st[v * 8], &st[(n_stats + v) * 8], &st[(2 * n_stats + v) * 8]};
         if (!q[0][0] && !q[1][0] && !q[2][0]) continue;
         while (ti < n_ids && ids_host[ti] < v) ++ti;
-        if (ti == n_ids || ids_host[ti] != v) {
-            cleanup();
+        if (ti == n_ids || ids_host[ti] != v)
             return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: label value " + std::to_string(v) + " is not in the table");
-        }
         const int r = radius[ti];
         const int w0 = std::max(0, own0 - r), w1 = (int)std::min<int64_t>(E, (int64_t)own1 + r);       // the planes this label is read on
         // per buffer: present inside the window?  (segment planes; the lower halo lies below w1, the upper one above w0)
@@ -624,104 +582,21 @@ extern "C" int saber_smooth_labels_chunk(saber_engine* e, const void* lo_dev, in
         L.r = sm_make_taps(sm_label_sigma((double)counts_host[ti], scale), taps);
         taps.insert(taps.end(), SM_OPT - 1, 0.0f);
         L.ws_off = 0;
-        biggest = std::max(biggest, (int64_t)L.dz * L.dy * L.dx);
         labs.push_back(L);
         owns.push_back(make_int2(o_first - zlo, o_last - o_first + 1));
     }
     if (out_n_labels) *out_n_labels = (int)labs.size();
-    if (labs.empty()) { ENG_HIP_CLEANUP(e, hipStreamSynchronize(s)); cleanup(); return SABER_OK; }
-    // ---- groups of labels whose two fp32 boxes fit the workspace, as sm_run forms them; the winner covers the own planes only
-    int64_t total = 0;
-    for (auto& L : labs) total += 2 * (int64_t)L.dz * L.dy * L.dx;
-    const int64_t ws_floats = std::min(total, std::max<int64_t>(2 * biggest, (int64_t)1 << 28));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.ws, (size_t)ws_floats * 4));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.taps, taps.size() * 4));
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.labels, labs.size() * sizeof(SmLabel)));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.own, labs.size() * sizeof(int2)));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.prefix, 3 * (labs.size() + 1) * sizeof(int)));
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.winner, (size_t)n_own * 4));
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.winner, 0, (size_t)n_own * 4, s));
-    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_axis_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
-    ENG_HIP_CLEANUP(e, hipFuncSetAttribute((const void*)sm_conv_z_own_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_LIMIT));
     SmSegs segs;
     for (int b = 0; b < 3; ++b) { segs.base[b] = bufs[b]; segs.first[b] = first[b]; }
-    std::vector<int> prefix;
-    const size_t stride = labs.size() + 1;
-    size_t g0 = 0;
-    while (g0 < labs.size()) {
-        size_t g1 = g0;
-        int64_t used = 0;
-        int grmax = 0;
-        int64_t tiles[3] = {0, 0, 0};
-        prefix.assign(3 * stride, 0);
-        while (g1 < labs.size()) {
-            SmLabel& L = labs[g1];
-            const int64_t v2 = 2 * (int64_t)L.dz * L.dy * L.dx;
-            if (g1 > g0 && used + v2 > ws_floats) break;
-            const int64_t xch = (L.dx + 63) / 64;
-            const int64_t tx = (((int64_t)L.dz * L.dy + 3) / 4) * xch;
-            const int64_t ty = (int64_t)L.dz * ((L.dy + SM_TL - 1) / SM_TL) * xch;
-            const int64_t tz = (int64_t)L.dy * ((owns[g1].y + SM_TL - 1) / SM_TL) * xch;
-            if (tiles[0] + tx > 0x7fffffff || tiles[1] + ty > 0x7fffffff || tiles[2] + tz > 0x7fffffff) {
-                if (g1 == g0) { cleanup(); return eng_fail(e, SABER_ERR_INVALID, "smooth_labels_chunk: label too large"); }
-                break;
-            }
-            L.ws_off = used;
-            used += v2;
-            grmax = std::max(grmax, L.r);
-            const size_t i = g1 - g0;
-            prefix[0 * stride + i] = (int)tiles[0]; prefix[1 * stride + i] = (int)tiles[1]; prefix[2 * stride + i] = (int)tiles[2];
-            tiles[0] += tx; tiles[1] += ty; tiles[2] += tz;
-            ++g1;
-        }
-        const int ng = (int)(g1 - g0);
-        for (int a = 0; a < 3; ++a) prefix[a * stride + ng] = (int)tiles[a];
-        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.labels, labs.data() + g0, (size_t)ng * sizeof(SmLabel), hipMemcpyHostToDevice, s));
-        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.own, owns.data() + g0, (size_t)ng * sizeof(int2), hipMemcpyHostToDevice, s));
-        ENG_HIP_CLEANUP(e, hipMemcpyAsync(S.prefix, prefix.data(), prefix.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        const size_t lds_x = (size_t)4 * (64 + 2 * grmax) * sizeof(float);
-        if (elem_bytes == 1)
-            hipLaunchKernelGGL(sm_conv_x_seg_kernel<uint8_t>, dim3((unsigned)tiles[0]), dim3(256), lds_x, s, segs, H, W, (const SmLabel*)S.labels,
-                               (const int*)S.prefix, ng, (const float*)S.taps, S.ws);
-        else if (elem_bytes == 2)
-            hipLaunchKernelGGL(sm_conv_x_seg_kernel<uint16_t>, dim3((unsigned)tiles[0]), dim3(256), lds_x, s, segs, H, W, (const SmLabel*)S.labels,
-                               (const int*)S.prefix, ng, (const float*)S.taps, S.ws);
-        else
-            hipLaunchKernelGGL(sm_conv_x_seg_kernel<uint32_t>, dim3((unsigned)tiles[0]), dim3(256), lds_x, s, segs, H, W, (const SmLabel*)S.labels,
-                               (const int*)S.prefix, ng, (const float*)S.taps, S.ws);
-        const size_t lds = (size_t)(SM_TL + 2 * grmax) * SM_TX * sizeof(float);
-        hipLaunchKernelGGL((sm_conv_axis_kernel<0, false>), dim3((unsigned)tiles[1]), dim3(256), lds, s, (const SmLabel*)S.labels,
-                           (const int*)(S.prefix + stride), ng, (const float*)S.taps, S.ws, H, W, (uint32_t*)nullptr, (float*)nullptr);
-        hipLaunchKernelGGL(sm_conv_z_own_kernel, dim3((unsigned)tiles[2]), dim3(256), lds, s, (const SmLabel*)S.labels,
-                           (const int*)(S.prefix + 2 * stride), ng, (const int2*)S.own, (const float*)S.taps, (const float*)S.ws, H, W, own0, S.winner);
-        ENG_HIP_CLEANUP(e, hipGetLastError());
-        ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));                    // the descriptor / prefix host buffers are reused by the next group
-        g0 = g1;
-    }
-    hipLaunchKernelGGL(sm_cast_kernel, dim3((unsigned)std::min<int64_t>((n_own / 4 + 255) / 256 + 1, 1 << 16)), dim3(256), 0, s,
-                       (const uint32_t*)S.winner, out_dev, n_own);
-    ENG_HIP_CLEANUP(e, hipGetLastError());
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
-    cleanup();
-    return SABER_OK;
+    return sm_convolve(e, "smooth_labels_chunk", segs, elem_bytes, H, W, labs, owns, own0, taps, out_dev, n_own, nullptr, s);
 }
 
 extern "C" int saber_label_max(saber_engine* e, const void* labels_dev, int elem_bytes, int64_t n, uint32_t* out_max, void* stream) {
     if (!e) return SABER_ERR_INVALID;
     if (!labels_dev || !out_max || n <= 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4))
         return eng_fail(e, SABER_ERR_INVALID, "label_max: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    SmScratch S;
-    auto cleanup = [&]() { S.release(); };
     ENG_DEVICE(e);
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
-    label_max(labels_dev, elem_bytes, nullptr, 0, n, S.maxv, s);
-    ENG_HIP_CLEANUP(e, hipGetLastError());
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(out_max, S.maxv, 4, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
-    cleanup();
+    ENG_HIP(e, label_max_host(&labels_dev, &n, 1, elem_bytes, nullptr, 0, out_max, (hipStream_t)stream));
     return SABER_OK;
 }
 
@@ -730,26 +605,21 @@ extern "C" int saber_label_counts(saber_engine* e, const void* labels_dev, int e
     if (!e) return SABER_ERR_INVALID;
     if (!labels_dev || !counts_dev || Z <= 0 || H <= 0 || W <= 0 || n_counts <= 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4))
         return eng_fail(e, SABER_ERR_INVALID, "label_counts: bad argument");
-    if ((int64_t)Z * H * W >= (int64_t)0x7fffffff) return eng_fail(e, SABER_ERR_INVALID, "label_counts: volumes of 2^31 voxels or more are not supported");
+    const int64_t n = (int64_t)Z * H * W;
+    if (n >= (int64_t)0x7fffffff) return eng_fail(e, SABER_ERR_INVALID, "label_counts: volumes of 2^31 voxels or more are not supported");
     if ((int64_t)n_counts > (int64_t)SM_MAX_LABEL + 1) return eng_fail(e, SABER_ERR_INVALID, "label_counts: label values above 2^22 are not supported");
     hipStream_t s = (hipStream_t)stream;
-    SmScratch S;
-    auto cleanup = [&]() { S.release(); };
     ENG_DEVICE(e);
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.maxv, 4));
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.maxv, 0, 4, s));
-    label_max(labels_dev, elem_bytes, nullptr, 0, (int64_t)Z * H * W, S.maxv, s);
     uint32_t maxv = 0;
-    ENG_HIP_CLEANUP(e, hipMemcpyAsync(&maxv, S.maxv, 4, hipMemcpyDeviceToHost, s));
-    ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
-    if (maxv >= (uint32_t)n_counts) {                                // the statistics kernel indexes its table by label value
-        cleanup();
+    ENG_HIP(e, label_max_host(&labels_dev, &n, 1, elem_bytes, nullptr, 0, &maxv, s));
+    if (maxv >= (uint32_t)n_counts)                                  // the statistics kernel indexes its table by label value
         return eng_fail(e, SABER_ERR_INVALID, "label_counts: label value " + std::to_string(maxv) + " does not fit a table of " + std::to_string(n_counts));
-    }
-    ENG_HIP_CLEANUP(e, hipMalloc(&S.stats, (size_t)n_counts * 32));
-    ENG_HIP_CLEANUP(e, hipMemsetAsync(S.stats, 0, (size_t)n_counts * 32, s));
-    label_stats(labels_dev, elem_bytes, nullptr, Z, H, W, S.stats, s);
-    hipLaunchKernelGGL(sm_counts_kernel, dim3((unsigned)((n_counts + 255) / 256)), dim3(256), 0, s, (const uint32_t*)S.stats, n_counts, counts_dev);
+    uint32_t* stats = nullptr;
+    auto cleanup = [&]() { (void)hipFree(stats); };
+    ENG_HIP_CLEANUP(e, hipMalloc(&stats, (size_t)n_counts * 32));
+    ENG_HIP_CLEANUP(e, hipMemsetAsync(stats, 0, (size_t)n_counts * 32, s));
+    sm_launch_stats(labels_dev, elem_bytes, nullptr, Z, H, W, stats, s);
+    hipLaunchKernelGGL(sm_counts_kernel, dim3((unsigned)((n_counts + 255) / 256)), dim3(256), 0, s, (const uint32_t*)stats, n_counts, counts_dev);
     ENG_HIP_CLEANUP(e, hipGetLastError());
     ENG_HIP_CLEANUP(e, hipStreamSynchronize(s));
     cleanup();
